@@ -23,7 +23,20 @@ value is the joined form rbc/rbc.go:88 returns (k*S contiguous bytes per
 instance); --row-view times the row view instead (the k data rows of the
 shard set, no join), and a shorter second run reports the other form.
 
-Host-fed leg (every rank, after the device-resident timing; key
+A plain run (`bench.py --gpus 1 --steps N --warmup W`) sets up, warms up,
+times the N steps and prints the headline line: metric, value, ms_per_step,
+the configuration, the timed steps' own event spans (stage_ms) and the ranks'
+records.  --dump-outputs DIR also writes what the last timed step computed
+(dump_outputs below; the inputs are seeded, so two builds can be compared
+array for array).  Everything else runs only under --full, after the timed
+steps unless noted: the isolated serial steps (before the warmup), the
+correctness guard (every instance decoded to its input, the poisoned receive,
+roots / digests against the C oracle, the gathered records; exit 3 when it
+fails), the second value-form leg, the rooflines, the CPU baseline, the
+host-fed epoch and the batcher sweep.  The --no-* switches below trim a
+--full run.
+
+Host-fed leg (--full; every rank, after the device-resident timing; key
 pcie_inclusive, never `value`): one epoch of the rank's instances through the
 C ABI from pinned NUMA-local host memory -- rbc_shard_commit,
 rbc_validate_packed_leaves of every received ECHO and
@@ -92,6 +105,12 @@ def parse_args(argv):
     ap.add_argument("--steps", type=int, default=150,
                     help="timed steps (the default keeps ~1 s of GPU work in the timed region at C2)")
     ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run every check and secondary measurement (see the module "
+                         "docstring); without it the run only times the steps and prints the headline line")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="write what the last timed step computed as DIR/<name>.npy (float32; seeded samples of "
+                         "the large arrays, at most 64 MB in all)")
     ap.add_argument("--config", default="c2", choices=sorted(CONFIGS))
     ap.add_argument("--instances", type=int, default=0, help="instances per GPU (weak scaling; default per config)")
     ap.add_argument("--total-instances", type=int, default=0,
@@ -369,7 +388,7 @@ def run(args, world, rank, local_rank, wd, out):
     # rocprof trace holds: under the pipeline a kernel's span also holds the
     # other stream's work, so the roofline carries both figures
     iso = None
-    if pipe and not args.no_isolated:
+    if pipe and args.full and not args.no_isolated:
         wd.enter("isolated steps", 300)
         for _ in range(2):
             step(None)
@@ -390,6 +409,57 @@ def run(args, world, rank, local_rank, wd, out):
     barrier()
     elapsed = time.perf_counter() - t0
     elapsed_max = rdz.max(elapsed)
+    ms_per_step = elapsed_max * 1000.0 / args.steps
+    value = total * n * S * args.steps / elapsed_max / 1e9
+    if args.dump_outputs and rank == 0:
+        # the last timed step's results, before anything else touches their buffers: the commit of batch t,
+        # the receive step's verify + decode of t-1 and its recheck + digest of t-2 (serial: one batch)
+        wd.enter("dump outputs", 300)
+        t_last = warm + args.steps - 1
+        dump_outputs(args.dump_outputs, I, n, k, d, B, S, spitch, opitch, args.join,
+                     commit=sets[t_last % nsets], cur_set=sets[(t_last - 1) % nsets],
+                     cur=rxb[(t_last - 1) % nrx], prev=rxb[(t_last - 2) % nrx])
+    stage_ms = spans(ev_sets[: args.steps], args.faults_on if pipe else None, pverify)
+    host = launch.host_info()
+    head = {
+        "metric": METRIC, "value": round(value, 3), "unit": "GB/s", "n_gpus": world, "steps": args.steps,
+        "warmup": warm, "ms_per_step": round(ms_per_step, 4), "higher_is_better": True, "scaling": scaling,
+        "vs_baseline": None,  # BASELINE.md publishes no number for this metric
+        "vs_baseline_basis": "none published (BASELINE.md); GPU / CPU port on the same host: --full, "
+                             "cpu_baseline.gpu_over_cpu",
+        "dtype": "u8",
+        "data": "synthetic (device-generated splitmix64 bytes per instance, seeded; 10% of instances with one "
+                "corrupted ECHO shard)",
+        "config": {"workload": f"{args.config}: {desc}, {total} instances ({I} on this rank); shard+commit, "
+                               "ECHO verify of the N-f received shards, interpolate from the first k valid",
+                   "n": n, "f": f, "value_bytes": B, "shard_bytes": S, "instances_total": total,
+                   "instances_per_gpu": I,
+                   "parallelism": f"instances partitioned over {world} GPU(s) in contiguous blocks"
+                                  + (", RCCL all-gather of {root,digest} records" if gather else ""),
+                   "gf_codec": ctx.codec,
+                   "wave_priority": {"commit": tx, "receive": rx, "decode_gemv": gv, "decode_reencode": rv},
+                   "value_form": "joined (k*S contiguous bytes per instance, the []byte rbc/rbc.go:88 returns)"
+                                 if args.join else "row view (the k data rows of the shard set, no join)",
+                   "faults_on": args.faults_on, "verify_on": "proposer" if pverify else "receiver",
+                   "hbm_plan": plan,
+                   **({"rehearsal": "all ranks on device 0, no RCCL (not a multi-GPU measurement)"}
+                      if args.rehearse_on_one_gpu else {}),
+                   "pipeline": (f"commit(t) || receive step: verify(t-1) + rehash(t-2) in one SHA launch, "
+                                f"recheck(t-2), decode(t-1) (rbc_dev_receive_step), two streams, {nsets} shard "
+                                "sets") if pipe else "serial"},
+        "full": args.full, "rccl": rccl, "library": ca.rbc.library_path(),
+        "host": {kk: host[kk] for kk in ("cpu_model", "nproc", "cgroup_cpu_quota", "affinity_cpus")},
+    }
+    if not args.full:
+        # the plain run ends here: the timed steps' own event spans and the ranks' records, no checks
+        ranks, skew = rank_timing(rdz, me, elapsed, args.steps, stage_ms)
+        wd.leave()
+        if rank == 0:
+            print(json.dumps({**head, "stage_ms": {kk: round(v, 4) for kk, v in stage_ms.items()},
+                              "ranks": ranks, "rank_skew": skew}), file=out, flush=True)
+        rdz.barrier()
+        rdz.close()
+        return 0
     wd.enter("checks", 600)
     if pipe:  # complete the batch the last receive step decoded (outside the timed region)
         x_last, cur = pending.popitem()
@@ -401,7 +471,6 @@ def run(args, world, rank, local_rank, wd, out):
         rstream.sync()
     else:
         last, rb_last = sets[0], rxb[0]
-    stage_ms = spans(ev_sets[: args.steps], args.faults_on if pipe else None, pverify)
     timed = check_batch(args, ca, dev, stream, I, n, k, B, S, spitch, vpitch, opitch, d_values, last, rb_last,
                         d_count)
 
@@ -478,12 +547,9 @@ def run(args, world, rank, local_rank, wd, out):
         wd.enter("second value-form leg", 300)
         second = second_form_leg()
 
-    ms_per_step = elapsed_max * 1000.0 / args.steps
-    value = total * n * S * args.steps / elapsed_max / 1e9
     wd.enter("report", 1200)
     rep = report(args, ctx, I, n, k, d, S, present_h, corrupt_h, stage_ms, iso, elapsed_max)
     cpu = None
-    host = launch.host_info()
     if rank == 0 and world == 1 and not args.no_cpu_baseline:
         cpu = cpu_baseline(args, host)
         cpu["gpu_over_cpu"] = round(value / cpu["value"], 2)
@@ -529,34 +595,9 @@ def run(args, world, rank, local_rank, wd, out):
         batcher = batcher_sweep(cpu)
     ranks, skew = rank_timing(rdz, me, elapsed, args.steps, stage_ms)
     line = {
-        "metric": METRIC, "value": round(value, 3), "unit": "GB/s", "n_gpus": world, "steps": args.steps,
-        "warmup": warm, "ms_per_step": round(ms_per_step, 4), "higher_is_better": True, "scaling": scaling,
-        "vs_baseline": None,  # BASELINE.md publishes no number for this metric
-        "vs_baseline_basis": "none published (BASELINE.md); GPU / CPU port on this box: cpu_baseline.gpu_over_cpu",
-        "dtype": "u8",
-        "data": "synthetic (device-generated splitmix64 bytes per instance, seeded; 10% of instances with one "
-                "corrupted ECHO shard)",
-        "config": {"workload": f"{args.config}: {desc}, {total} instances ({I} on this rank); shard+commit, "
-                               "ECHO verify of the N-f received shards, interpolate from the first k valid",
-                   "n": n, "f": f, "value_bytes": B, "shard_bytes": S, "instances_total": total,
-                   "instances_per_gpu": I,
-                   "parallelism": f"instances partitioned over {world} GPU(s) in contiguous blocks"
-                                  + (", RCCL all-gather of {root,digest} records" if gather else ""),
-                   "gf_codec": ctx.codec,
-                   "wave_priority": {"commit": tx, "receive": rx, "decode_gemv": gv, "decode_reencode": rv},
-                   "value_form": "joined (k*S contiguous bytes per instance, the []byte rbc/rbc.go:88 returns)"
-                                 if args.join else "row view (the k data rows of the shard set, no join)",
-                   "faults_on": args.faults_on, "verify_on": "proposer" if pverify else "receiver",
-                   "hbm_plan": plan,
-                   **({"rehearsal": "all ranks on device 0, no RCCL (not a multi-GPU measurement)"}
-                      if args.rehearse_on_one_gpu else {}),
-                   "pipeline": (f"commit(t) || receive step: verify(t-1) + rehash(t-2) in one SHA launch, "
-                                f"recheck(t-2), decode(t-1) (rbc_dev_receive_step), two streams, {nsets} shard "
-                                "sets") if pipe else "serial"},
-        **rep, **checks, "cpu_baseline": cpu, "pcie_inclusive": pcie, "rccl": rccl, "ranks": ranks,
-        "rank_skew": skew, "library": ca.rbc.library_path(), **({"value_row_view": second} if args.join else {"value_joined": second}),
-        "batcher": batcher,
-        "host": {kk: host[kk] for kk in ("cpu_model", "nproc", "cgroup_cpu_quota", "affinity_cpus")},
+        **head,
+        **rep, **checks, "cpu_baseline": cpu, "pcie_inclusive": pcie, "ranks": ranks, "rank_skew": skew,
+        **({"value_row_view": second} if args.join else {"value_joined": second}), "batcher": batcher,
     }
     ok = all(checks[c] for c in ("values_ok", "oracle_sample_ok", "gather_ok")) and checks["decoded_ok"] == total
     if pcie is not None:  # every rank's host-fed verdicts, values and roots
@@ -576,6 +617,56 @@ def run(args, world, rank, local_rank, wd, out):
     rdz.barrier()
     rdz.close()
     return 0
+
+
+DUMP_ELEMS = {"value": 6 << 20, "shards": 4 << 20, "valid": 2 << 20, "branches": 1 << 20}  # float32 each: < 64 MB
+
+
+def dump_outputs(path, I, n, k, d, B, S, spitch, opitch, join, commit, cur_set, cur, prev):
+    """--dump-outputs: what the last timed step left on the device, as
+    float32 .npy files of byte values (status: the int32 codes).  roots,
+    digests and status hold every instance; the large arrays a seeded sample
+    whose indices are written beside them, the same from run to run:
+      commit_roots [I,32], commit_branches [instances,N,depth,32],
+      commit_shards [rows,S] (rows of commit_shards_index: instance, shard)
+                       -- the step's commit (batch t)
+      receive_valid [instances,N], receive_value [instances,B]
+                       -- its ECHO verdicts and decoded values (batch t-1)
+      receive_digests [I,32], receive_status [I]
+                       -- its root recheck and digest (batch t-2)
+    Under the serial schedule all three are the one batch of the step."""
+    os.makedirs(path, exist_ok=True)
+    rng = np.random.default_rng(SEED + 3)
+    dd = max(d, 1)
+
+    def pick(count, limit):
+        return np.sort(rng.choice(count, size=max(1, min(count, limit)), replace=False))
+
+    def save(name, a):
+        np.save(os.path.join(path, name + ".npy"), np.ascontiguousarray(a, dtype=np.float32))
+
+    save("commit_roots", commit["roots"].download(I * 32).reshape(I, 32))
+    save("receive_digests", prev["digests"].download(I * 32).reshape(I, 32))
+    save("receive_status", prev["status"].download(I * 4).view(np.int32))
+    ib = pick(I, DUMP_ELEMS["branches"] // (n * dd * 32))
+    save("commit_branches_index", ib)
+    save("commit_branches", np.stack([commit["branches"].download(n * dd * 32, int(i) * n * dd * 32)
+                                      for i in ib]).reshape(len(ib), n, dd, 32))
+    rows = pick(I * n, min(2048, DUMP_ELEMS["shards"] // S))
+    save("commit_shards_index", np.stack([rows // n, rows % n], axis=1))
+    save("commit_shards", np.stack([commit["shards"].download(S, int(r) * spitch) for r in rows]))
+    iv = pick(I, DUMP_ELEMS["valid"] // n)
+    save("receive_valid_index", iv)
+    save("receive_valid", cur["valid"].download(I * n).reshape(I, n) if len(iv) == I
+         else np.stack([cur["valid"].download(n, int(i) * n) for i in iv]))
+    io = pick(I, DUMP_ELEMS["value"] // B)
+    save("receive_value_index", io)
+    if join:
+        vals = [cur["out"].download(B, int(i) * opitch) for i in io]
+    else:  # the row view: the k data rows of the batch's shard set, joined here and cut to the value's length
+        vals = [cur_set["shards"].download(k * spitch, int(i) * n * spitch).reshape(k, spitch)[:, :S].reshape(-1)[:B]
+                for i in io]
+    save("receive_value", np.stack(vals))
 
 
 def _run_key(name):

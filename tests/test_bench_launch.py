@@ -288,6 +288,49 @@ def test_value_form_defaults_to_the_joined_value():
     assert bench.parse_args(["--no-joined-leg"]).no_second_form is True
 
 
+def test_a_plain_run_is_not_full():
+    import bench
+    a = bench.parse_args(["--gpus", "1", "--steps", "7", "--warmup", "2"])
+    assert a.full is False and a.dump_outputs == "" and a.steps == 7 and a.warmup == 2
+    a = bench.parse_args(["--full", "--dump-outputs", "somewhere"])
+    assert a.full is True and a.dump_outputs == "somewhere"
+
+
+class _Buf:
+    """Stands in for a DeviceBuffer: sized, bounds-checked, all zero."""
+
+    def __init__(self, nbytes):
+        self.nbytes = nbytes
+
+    def download(self, nbytes=None, offset=0):
+        import numpy as np
+        nbytes = self.nbytes - offset if nbytes is None else nbytes
+        assert 0 <= offset and offset + nbytes <= self.nbytes
+        return np.zeros(nbytes, np.uint8)
+
+
+def test_dumped_outputs_fit_64_mb_at_every_config(tmp_path):
+    """--dump-outputs at each config's default size, both value forms, on
+    stand-in buffers: every read stays inside its buffer, every array is
+    float32, and the files together stay under 64 MB."""
+    import numpy as np
+    import bench
+    for cfg, (n, f, B, I, _) in bench.CONFIGS.items():
+        k, d = n - 2 * f, max(1, (n - 1).bit_length())
+        S = (B + k - 1) // k
+        spitch, opitch = bench.round_up(S, 128), bench.round_up(k * S, 16)
+        sp = dict(shards=_Buf(I * n * spitch), roots=_Buf(I * 32), branches=_Buf(I * n * d * 32))
+        for join in (True, False):
+            rb = dict(valid=_Buf(I * n), digests=_Buf(I * 32), status=_Buf(I * 4), out=_Buf(I * opitch) if join else None)
+            out = tmp_path / f"{cfg}-{int(join)}"
+            bench.dump_outputs(str(out), I, n, k, d, B, S, spitch, opitch, join, commit=sp, cur_set=sp, cur=rb, prev=rb)
+            arrays = {p.name: np.load(p) for p in out.iterdir()}
+            assert len(arrays) == 11 and all(a.dtype == np.float32 for a in arrays.values())
+            assert sum(a.nbytes for a in arrays.values()) <= 64e6 and sum(p.stat().st_size for p in out.iterdir()) <= 64e6
+            assert arrays["receive_value.npy"].shape[1] == B and arrays["commit_shards.npy"].shape[1] == S
+            assert arrays["commit_roots.npy"].shape == (I, 32) and arrays["receive_status.npy"].shape == (I,)
+
+
 def test_profile_files_are_taken_newest_run_first():
     """The bench takes PMC traffic and clock files from the newest run of a
     round: runs are lettered a..z, then aa, ab, ... (r06ae after r06h)."""

@@ -19,9 +19,10 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 QUICK = ["--no-cpu-baseline", "--no-pcie", "--oracle-samples", "4"]
 
 
-def _run(args, timeout=300, env=None):
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py")] + args, capture_output=True, text=True,
-                       timeout=timeout, env=env)
+def _run(args, timeout=300, env=None, full=True):
+    """The guard, the rooflines and every secondary leg run under --full."""
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py")] + (["--full"] if full else []) + args,
+                       capture_output=True, text=True, timeout=timeout, env=env)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.strip()]
     assert len(lines) == 1, r.stdout
@@ -50,6 +51,89 @@ def test_bench_schedules_pass_their_guard(pipeline, join):
         assert rd["avg_ms"] > 0 and 0 < rd["frac"] < 1 and rd["algorithmic_bytes_per_launch"] > 0
         # C2 walks the branches inside the row hashing: one launch, no shared-path span
         assert d["roofline_verify"]["kernel"] == "sha_rx_kernel<verify+regen>" and d["roofline_verify_path"] is None
+
+
+PLAIN_FORMS = {"pipelined-joined": [], "serial-row-view": ["--pipeline", "0", "--row-view"]}
+DUMPED = ("commit_roots", "commit_branches", "commit_branches_index", "commit_shards", "commit_shards_index",
+          "receive_valid", "receive_valid_index", "receive_value", "receive_value_index", "receive_digests",
+          "receive_status")
+
+
+@pytest.fixture(scope="module")
+def plain_runs(tmp_path_factory):
+    """One plain run (no --full) per schedule / value form, 96 instances, each with --dump-outputs."""
+    import numpy as np
+    runs = {}
+    for name, extra in PLAIN_FORMS.items():
+        out = tmp_path_factory.mktemp(name)
+        line = _run(["--gpus", "1", "--steps", "3", "--warmup", "3", "--instances", "96", "--dump-outputs", str(out)]
+                    + extra, full=False)
+        assert sorted(os.listdir(out)) == sorted(x + ".npy" for x in DUMPED)
+        runs[name] = (line, {x: np.load(out / (x + ".npy")) for x in DUMPED})
+    return runs
+
+
+@pytest.mark.parametrize("form", sorted(PLAIN_FORMS))
+def test_plain_run_prints_the_headline_only(plain_runs, form):
+    """Without --full the bench times its steps and stops: the contract keys
+    and the timed steps' own spans, none of the checks or secondary legs."""
+    d, _ = plain_runs[form]
+    for key in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "dtype",
+                "config", "stage_ms", "ranks", "library"):
+        assert key in d, key
+    for key in ("guard", "decoded_ok", "roofline", "cpu_baseline", "pcie_inclusive", "batcher", "value_row_view",
+                "value_joined", "commit_only"):
+        assert key not in d, key
+    assert d["full"] is False and d["steps"] == 3 and d["unit"] == "GB/s" and d["higher_is_better"] is True
+    c = d["config"]
+    # value is the committed shard bytes of one step over ms_per_step
+    step_bytes = c["instances_total"] * c["n"] * c["shard_bytes"]
+    assert d["value"] == pytest.approx(step_bytes / d["ms_per_step"] / 1e6, rel=1e-3)
+    assert c["hbm_plan"]["schedule"] == ("serial" if form.startswith("serial") else "pipelined")
+
+
+@pytest.mark.parametrize("form", sorted(PLAIN_FORMS))
+def test_dumped_outputs_are_the_steps_results(plain_runs, ref, form):
+    """--dump-outputs: float32 arrays within 64 MB; every instance decoded, the
+    sampled values equal their seeded inputs, the ECHO verdicts are the
+    present mask less the corrupted shard, and sampled roots, branches, shards
+    and digests equal the C oracle's."""
+    import numpy as np
+    import bench
+    from cleisthenes_amd import synth
+    d, a = plain_runs[form]
+    c = d["config"]
+    n, f, B, S, I = c["n"], c["f"], c["value_bytes"], c["shard_bytes"], 96
+    k = n - 2 * f
+    assert all(x.dtype == np.float32 for x in a.values()) and sum(x.nbytes for x in a.values()) <= 64e6
+    assert a["commit_roots"].shape == (I, 32) and a["receive_digests"].shape == (I, 32)
+    assert a["receive_status"].shape == (I,) and not a["receive_status"].any()
+    vpitch = bench.round_up(k * S + 32, 64)
+    for row, i in zip(a["receive_value"], a["receive_value_index"].astype(int)):
+        assert np.array_equal(row, synth.row(bench.SEED, i, vpitch, B))
+    valid = a["receive_valid"]
+    assert valid.shape == (len(a["receive_valid_index"]), n) and set(np.unique(valid)) <= {0.0, 1.0}
+    per = valid.sum(axis=1)
+    assert set(per.tolist()) == {n - f, n - f - 1} and 0 < (per == n - f - 1).sum() < 0.3 * I  # ~10 % corrupted
+    com = {}
+    for i in set(a["commit_branches_index"].astype(int)[:2]) | set(a["commit_shards_index"].astype(int)[:2, 0]):
+        com[i] = ref.encode_commit(n, f, synth.row(bench.SEED, i, vpitch, B))  # shards, root, branches, leaves
+        assert bytes(a["commit_roots"][i].astype(np.uint8)) == com[i][1]
+        dig = ref.sha256(np.ascontiguousarray(com[i][3][:k]).tobytes())
+        assert bytes(a["receive_digests"][i].astype(np.uint8)) == dig
+    for br, i in list(zip(a["commit_branches"], a["commit_branches_index"].astype(int)))[:2]:
+        assert np.array_equal(br.reshape(-1), np.asarray(com[i][2], dtype=np.uint8).reshape(-1))
+    for sh, (i, j) in list(zip(a["commit_shards"], a["commit_shards_index"].astype(int)))[:2]:
+        assert np.array_equal(sh, com[i][0][j])
+
+
+def test_dumped_outputs_do_not_depend_on_the_schedule(plain_runs):
+    """The inputs and the samples are seeded: the serial row-view run and the
+    pipelined joined run dump the same arrays, element for element."""
+    import numpy as np
+    (_, a), (_, b) = plain_runs["pipelined-joined"], plain_runs["serial-row-view"]
+    for x in DUMPED:
+        assert np.array_equal(a[x], b[x]), x
 
 
 def test_bench_c3_8192_instances_on_one_gpu():
@@ -179,8 +263,8 @@ def test_bench_guard_fails_a_build_that_never_regenerates(config, join):
     absent slots and pass, but the poisoned receive cannot, so bench.py exits
     3 with values_ok and decoded_ok false -- and names the mutant it mapped."""
     assert os.path.exists(MUTANT), "build() makes tests/mutants"
-    args = [sys.executable, os.path.join(ROOT, "bench.py"), "--config", config, "--instances", "64", "--steps", "3",
-            "--warmup", "3", "--no-isolated"] + QUICK + ([] if join else ["--row-view"])
+    args = [sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--config", config, "--instances", "64",
+            "--steps", "3", "--warmup", "3", "--no-isolated"] + QUICK + ([] if join else ["--row-view"])
     r = subprocess.run(args, capture_output=True, text=True, timeout=300, env=dict(os.environ, RBC_GPU_LIB=MUTANT))
     assert r.returncode == 3, (r.returncode, r.stderr[-3000:])
     err = [ln for ln in r.stderr.splitlines() if ln.startswith('{"error"')]

@@ -12,11 +12,11 @@ OUT=$ROOT/gpurun_out/pmc_$TAG
 mkdir -p "$OUT"
 cd /tmp && export TMPDIR=/tmp
 timeout -k 10 300 rocprofv3 --kernel-trace --stats -d "$OUT/trace" -o run --output-format csv -- \
-    python3 "$ROOT/bench.py" $ARGS > "$OUT/trace.json" 2> "$OUT/trace.log"
+    python3 "$ROOT/bench.py" --full $ARGS > "$OUT/trace.json" 2> "$OUT/trace.log"
 pass() {  # pass <name> <counters...>
     local name=$1; shift
     timeout -s KILL 180 rocprofv3 --pmc "$@" -d "$OUT/$name" -o run --output-format csv -- \
-        python3 "$ROOT/bench.py" $ARGS > "$OUT/$name.json" 2> "$OUT/$name.log"
+        python3 "$ROOT/bench.py" --full $ARGS > "$OUT/$name.json" 2> "$OUT/$name.log"
 }
 # PASSES (default all): a subset, e.g. PASSES="fetch write" for the traffic alone
 want() { [ -z "${PASSES:-}" ] || [[ " $PASSES " == *" $1 "* ]]; }

@@ -12,11 +12,11 @@ OUT=$ROOT/gpurun_out/prof_$TAG
 mkdir -p "$OUT"
 cd /tmp && export TMPDIR=/tmp
 timeout -k 10 300 rocprofv3 --kernel-trace --stats -d "$OUT/trace" -o run --output-format csv -- \
-    python3 "$ROOT/bench.py" $ARGS > "$OUT/trace.json" 2> "$OUT/trace.log"
+    python3 "$ROOT/bench.py" --full $ARGS > "$OUT/trace.json" 2> "$OUT/trace.log"
 pass() {  # pass <name> <counters...>
     local name=$1; shift
     timeout -s KILL 180 rocprofv3 --pmc "$@" -d "$OUT/$name" -o run --output-format csv -- \
-        python3 "$ROOT/bench.py" $ARGS --no-cpu-baseline --no-pcie > "$OUT/$name.json" 2> "$OUT/$name.log"
+        python3 "$ROOT/bench.py" --full $ARGS --no-cpu-baseline --no-pcie > "$OUT/$name.json" 2> "$OUT/$name.log"
 }
 if [ -z "${NO_PMC:-}" ]; then
 pass sq1 SQ_WAVES SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_INSTS_VALU GRBM_GUI_ACTIVE
