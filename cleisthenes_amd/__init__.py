@@ -17,6 +17,8 @@ from .rbc import (  # noqa: F401
     Event,
     device_count,
     pinned_empty,
+    split_rows,
 )
 
-__all__ = ["Batcher", "Context", "DeviceBuffer", "Encoder", "RBCError", "Stream", "Event", "device_count", "pinned_empty"]
+__all__ = ["Batcher", "Context", "DeviceBuffer", "Encoder", "RBCError", "Stream", "Event", "device_count", "pinned_empty",
+           "split_rows"]

@@ -180,6 +180,14 @@ _SIGS = {
     "rbc_val_message_size": (c_size_t, [c_int, c_uint32, c_uint32, c_int]),
     "rbc_shard_commit_val": (c_int, [c_void_p, c_int, c_void_p, szp, c_void_p, c_size_t, u32p, c_void_p,
                                      POINTER(c_uint64)]),
+    # parity-only shard commit (RBC_HAS_SHARD_COMMIT_PARITY)
+    "rbc_dev_shard_commit_parity": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_uint64, c_void_p, c_uint32,
+                                            c_void_p, c_void_p, c_uint32, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "rbc_shard_commit_parity": (c_int, [c_void_p, c_int, c_void_p, szp, c_void_p, c_size_t, u32p, c_void_p,
+                                        c_void_p, POINTER(c_uint64)]),
+    "rbc_shard_parity": (c_int, [c_void_p, c_void_p, c_size_t, c_void_p, c_size_t, szp, c_void_p, c_void_p]),
+    "rbc_split_tail_bytes": (c_size_t, [c_int, c_size_t]),
+    "rbc_split_rows": (c_int, [c_int, c_void_p, c_size_t, c_void_p, c_size_t, POINTER(c_void_p), szp, szp]),
     "rbc_node_create": (c_int, [c_void_p, c_int, c_int, c_int, c_int, POINTER(c_void_p)]),
     "rbc_node_destroy": (None, [c_void_p]),
     "rbc_node_propose": (c_int, [c_void_p, c_void_p, c_size_t]),

@@ -130,7 +130,7 @@ struct Ws {
 // buffers at completion (rbc_wait / rbc_poll / slot reuse).
 struct Slot {
     DevBuf d_values, d_shards, d_leaves, d_roots, d_branches, d_valid, d_status, d_digests, d_lens, d_slens, d_idx,
-        d_offs, d_present, d_pack;
+        d_offs, d_present, d_pack, d_parity;  // d_parity: rbc_shard_commit_parity's dense arena [count][p][pitch]
     DevBuf h_in{nullptr, 0, true}, h_out{nullptr, 0, true};
     Ws ws;
     hipStream_t stream = nullptr;
@@ -153,7 +153,7 @@ struct Slot {
     int d2h_rc = 0;
     void release() {
         for (DevBuf *b : {&d_values, &d_shards, &d_leaves, &d_roots, &d_branches, &d_valid, &d_status, &d_digests,
-                          &d_lens, &d_slens, &d_idx, &d_offs, &d_present, &d_pack, &h_in, &h_out})
+                          &d_lens, &d_slens, &d_idx, &d_offs, &d_present, &d_pack, &d_parity, &h_in, &h_out})
             b->release();
         ws.release();
         if (stream) (void)hipStreamDestroy(stream);
@@ -341,6 +341,98 @@ int stage_leaves(rbc_ctx *c, hipStream_t st, int count, const uint8_t *shards, u
     a.depth = c->depth;
     a.prio = c->tx_prio;
     RBC_HIP(rbc_launch_sha_rows(a, false, st));
+    return RBC_OK;
+}
+
+// stage_encode with two outputs (rbc_dev_shard_commit_parity): the k data rows
+// to data_rows [count][k][pitch], the p parity rows to the dense arena parity
+// [count][p][pitch].  Same argument rules as stage_encode.
+int stage_encode_parity(rbc_ctx *c, hipStream_t st, int count, const uint8_t *values, uint64_t value_pitch,
+                        const uint32_t *value_lens, uint32_t uniform_value_len, uint8_t *data_rows, uint8_t *parity,
+                        uint32_t pitch) {
+    if (count < 0 || (count > 0 && (!values || !data_rows || (c->p > 0 && !parity)))) return RBC_ERR_INVALID_ARG;
+    if (pitch == 0 || pitch % kAlign) return RBC_ERR_INVALID_ARG;
+    if (!value_lens) {
+        if (uniform_value_len == 0) return RBC_ERR_SHORT_DATA;
+        const size_t S = (uniform_value_len + c->k - 1) / c->k;
+        if (S > pitch || value_pitch < round_up((size_t)c->k * S, 16) + 16) return RBC_ERR_INVALID_ARG;
+    }
+    if (value_pitch > 0x7fffffffULL || (uint64_t)c->n * pitch > 0x7fffffffULL) return RBC_ERR_INVALID_ARG;
+    if (count == 0) return RBC_OK;
+    if (c->fft) {
+        FftArgs a{};
+        a.count = count;
+        a.n = c->n;
+        a.k = c->k;
+        a.mode = GF_MODE_ENCODE_PARITY;
+        a.values = values;
+        a.value_pitch = (uint32_t)value_pitch;
+        a.shards = data_rows;
+        a.inst_pitch = (uint64_t)c->k * pitch;
+        a.row_pitch = pitch;
+        a.lens = value_lens;
+        a.uniform_len = uniform_value_len;
+        a.prio = c->tx_prio;
+        a.parity = parity;
+        a.parity_inst_pitch = (uint64_t)c->p * pitch;
+        RBC_HIP(rbc_launch_rs_fft(a, st));
+        return RBC_OK;
+    }
+    GfArgs g{};
+    g.count = count;
+    g.tiles = (int)((pitch + 4095) / 4096);
+    g.R = c->p;
+    g.K = c->k;
+    g.rc = rbc_gf_pick_rc(c->p > 0 ? c->p : 1, kGfRcMax);
+    g.mode = GF_MODE_ENCODE;
+    g.in = values;
+    g.in_inst_pitch = value_pitch;
+    g.in_inst_bytes = (uint32_t)value_pitch;
+    g.out = data_rows;  // not written: R rows go to the arena (p == 0: no output rows at all)
+    g.out_inst_pitch = (uint64_t)c->k * pitch;
+    g.out_row_pitch = pitch;
+    g.copy = data_rows;
+    g.lens = value_lens;
+    g.uniform_len = uniform_value_len;
+    g.coef = c->d_M + (size_t)c->k * c->k;
+    g.coef_inst_stride = 0;
+    g.prio = c->tx_prio;
+    g.parity = c->p > 0 ? parity : nullptr;
+    g.parity_inst_pitch = (uint64_t)c->p * pitch;
+    RBC_HIP(rbc_launch_gf_rows(g, st));
+    return RBC_OK;
+}
+
+// stage_leaves over the two buffers of stage_encode_parity: leaves [count][n][32]
+// as ever, slots 0..k-1 from the data rows and k..n-1 from the arena -- two
+// launches of the row hashing, each over a dense [count][rows][pitch] buffer.
+int stage_leaves_parity(rbc_ctx *c, hipStream_t st, int count, const uint8_t *data_rows, const uint8_t *parity,
+                        uint32_t pitch, const uint32_t *shard_lens, uint32_t uniform_shard_len, uint8_t *leaves) {
+    if (count < 0 || (count > 0 && (!data_rows || !leaves || (c->p > 0 && !parity)))) return RBC_ERR_INVALID_ARG;
+    if (pitch % kAlign || (!shard_lens && (uniform_shard_len == 0 || uniform_shard_len > pitch)))
+        return RBC_ERR_INVALID_ARG;
+    if (count == 0) return RBC_OK;
+    ShaArgs a{};
+    a.count = count;
+    a.row_pitch = pitch;
+    a.lens = shard_lens;
+    a.uniform_len = uniform_shard_len;
+    a.leaves_inst_pitch = (uint64_t)c->n * 32;
+    a.n = c->n;
+    a.depth = c->depth;
+    a.prio = c->tx_prio;
+    a.rows_per_inst = c->k;
+    a.rows = data_rows;
+    a.inst_pitch = (uint64_t)c->k * pitch;
+    a.leaves = leaves;
+    RBC_HIP(rbc_launch_sha_rows(a, false, st));
+    if (c->p > 0) {
+        a.rows_per_inst = c->p;
+        a.rows = parity;
+        a.inst_pitch = (uint64_t)c->p * pitch;
+        a.leaves = leaves + (size_t)32 * c->k;  // slot s of this launch is leaf k + s
+        RBC_HIP(rbc_launch_sha_rows(a, false, st));
+    }
     return RBC_OK;
 }
 
@@ -1284,6 +1376,24 @@ int rbc_dev_shard_commit(rbc_ctx *c, void *stream, int count, const uint8_t *val
     return stage_merkle_build(c, st, count, leaves, roots, branches);
 }
 
+int rbc_dev_shard_commit_parity(rbc_ctx *c, void *stream, int count, const uint8_t *values, uint64_t value_pitch,
+                                const uint32_t *value_lens, uint32_t uniform_value_len, uint8_t *data_rows,
+                                uint8_t *parity, uint32_t row_pitch, const uint32_t *shard_lens, uint8_t *leaves,
+                                uint8_t *roots, uint8_t *branches) {
+    if (!c) return RBC_ERR_INVALID_ARG;
+    if (value_lens && !shard_lens) return RBC_ERR_INVALID_ARG;
+    if (count > 0 && (!leaves || !roots)) return RBC_ERR_INVALID_ARG;  // before the first launch
+    RBC_HIP(hipSetDevice(c->device));
+    hipStream_t st = as_stream(stream);
+    int rc = stage_encode_parity(c, st, count, values, value_pitch, value_lens, uniform_value_len, data_rows, parity,
+                                 row_pitch);
+    if (rc) return rc;
+    const uint32_t uS = value_lens ? 0u : (uniform_value_len + c->k - 1) / c->k;
+    rc = stage_leaves_parity(c, st, count, data_rows, parity, row_pitch, shard_lens, uS, leaves);
+    if (rc) return rc;
+    return stage_merkle_build(c, st, count, leaves, roots, branches);
+}
+
 int rbc_dev_verify(rbc_ctx *c, void *stream, int count, const uint8_t *shards, uint32_t shard_pitch,
                    const uint32_t *shard_lens, uint32_t uniform_shard_len, const uint8_t *branches,
                    const uint8_t *roots, const uint8_t *present, uint8_t *valid, uint8_t *leaves) {
@@ -1683,6 +1793,112 @@ int rbc_shard_commit(rbc_ctx *c, int count, const uint8_t *const *values, const 
                 for (int j = 0; j < n; ++j)
                     memcpy(shards_out + ((size_t)i * n + j) * shard_pitch, o_sh + ((size_t)i * n + j) * dpitch, Smax);
             if (shard_lens_out) shard_lens_out[i] = (uint32_t)S;
+        });
+        if (!rt_direct) memcpy(roots_out, o_rt, (size_t)count * 32);
+        if (branches_out && d > 0 && !br_direct) memcpy(branches_out, o_br, br_out);
+        return RBC_OK;
+    }, d2h);
+}
+
+// rbc_shard_commit for a caller that keeps Split's data rows as slices of its
+// own value (klauspost Split / Encode, rbc/rbc.go:97-100): only the p parity
+// rows of each instance cross PCIe, from the dense arena the encoder wrote
+// them to ([count][p][dpitch], stage_encode_parity) in one linear copy.
+int rbc_shard_commit_parity(rbc_ctx *c, int count, const uint8_t *const *values, const size_t *value_lens,
+                            uint8_t *parity_out, size_t parity_pitch, uint32_t *shard_lens_out, uint8_t *roots_out,
+                            uint8_t *branches_out, uint64_t *ticket) {
+    if (!c || count < 0 || (count > 0 && (!values || !value_lens || !roots_out || (c->p > 0 && !parity_out))))
+        return RBC_ERR_INVALID_ARG;
+    if (count == 0) { if (ticket) *ticket = 0; return RBC_OK; }
+    size_t Smax = 0;
+    for (int i = 0; i < count; ++i) {
+        if (value_lens[i] == 0) return RBC_ERR_SHORT_DATA;  // Split: len(data) == 0
+        if (!values[i]) return RBC_ERR_INVALID_ARG;
+        Smax = std::max(Smax, (value_lens[i] + c->k - 1) / c->k);
+    }
+    const int d = c->depth, n = c->n, k = c->k, p = c->p;
+    if (p > 0 && parity_pitch < Smax) return RBC_ERR_INVALID_ARG;
+    const size_t vpitch = round_up((size_t)k * Smax + 32, kAlign);
+    if (vpitch > 0x7fffffffULL || (size_t)n * round_up(Smax, 128) > 0x7fffffffULL) return RBC_ERR_INVALID_ARG;
+    // the three output forms of rbc_shard_commit, over p rows per instance
+    const bool par_direct = p > 0 && host_pinned(parity_out, ((size_t)count * p - 1) * parity_pitch + Smax);
+    const bool par_flat = par_direct && parity_pitch % kAlign == 0 && parity_pitch <= 0x7fffffffULL / n &&
+                          host_pinned(parity_out, (size_t)count * p * parity_pitch);  // the flat copy's extent
+    const size_t dpitch = par_flat ? parity_pitch : round_up(Smax, 128);
+    const size_t par_bytes = (size_t)count * p * dpitch, br_bytes = (size_t)count * n * std::max(d, 1) * 32;
+    std::lock_guard<std::mutex> lk(c->mu);
+    RBC_HIP(hipSetDevice(c->device));
+    Slot *sp = acquire_slot(c);
+    if (!sp) return RBC_ERR_DEVICE;
+    Slot &s = *sp;
+    hipStream_t st = s.stream;
+    RBC_HIP(s.d_values.ensure((size_t)count * vpitch));
+    RBC_HIP(s.d_shards.ensure((size_t)count * k * dpitch));  // the data rows: hashed, never copied back
+    RBC_HIP(s.d_parity.ensure(par_bytes));
+    RBC_HIP(s.d_leaves.ensure((size_t)count * n * 32));
+    RBC_HIP(s.d_roots.ensure((size_t)count * 32));
+    RBC_HIP(s.d_branches.ensure(br_bytes));
+    RBC_HIP(s.d_lens.ensure((size_t)count * 8));
+    bool zc = false;
+    const bool in_direct = values_pinned(values, value_lens, count, &zc);
+    const size_t in_stage = in_direct ? 0 : (size_t)count * vpitch;
+    const bool rt_direct = host_pinned(roots_out, (size_t)count * 32);
+    const size_t br_out = (size_t)count * n * d * 32;
+    const bool br_direct = branches_out && d > 0 && host_pinned(branches_out, br_out);
+    RBC_HIP(s.h_in.ensure(in_stage + (size_t)count * 8 + (in_direct ? (size_t)count * 8 : 0)));
+    RBC_HIP(s.h_out.ensure((par_direct ? 0 : par_bytes) + (size_t)count * 32 + br_bytes));
+    uint8_t *stage = s.h_in.as<uint8_t>();
+    uint32_t *lens = reinterpret_cast<uint32_t *>(stage + in_stage);
+    if (in_direct) {
+        for (int i = 0; i < count; ++i) {
+            lens[i] = (uint32_t)value_lens[i];
+            lens[count + i] = (uint32_t)((value_lens[i] + k - 1) / k);
+        }
+        const int rc = upload_pinned_values(s, st, count, values, value_lens, vpitch, zc, lens,
+                                            reinterpret_cast<uint64_t *>(stage + in_stage + (size_t)count * 8));
+        if (rc) return rc;
+    } else {
+        parallel_for(count, vpitch, [&](int i) {
+            memcpy(stage + (size_t)i * vpitch, values[i], value_lens[i]);
+            memset(stage + (size_t)i * vpitch + value_lens[i], 0, vpitch - value_lens[i]);
+            lens[i] = (uint32_t)value_lens[i];
+            lens[count + i] = (uint32_t)((value_lens[i] + k - 1) / k);
+        });
+        RBC_HIP(hipMemcpyAsync(s.d_values.p, stage, (size_t)count * vpitch, hipMemcpyHostToDevice, st));
+    }
+    RBC_HIP(hipMemcpyAsync(s.d_lens.p, lens, (size_t)count * 8, hipMemcpyHostToDevice, st));
+    const uint32_t *d_vlens = s.d_lens.as<uint32_t>(), *d_slens = d_vlens + count;
+    int rc = stage_encode_parity(c, st, count, s.d_values.as<uint8_t>(), vpitch, d_vlens, 0, s.d_shards.as<uint8_t>(),
+                                 s.d_parity.as<uint8_t>(), (uint32_t)dpitch);
+    if (!rc) rc = stage_leaves_parity(c, st, count, s.d_shards.as<uint8_t>(), s.d_parity.as<uint8_t>(),
+                                      (uint32_t)dpitch, d_slens, 0, s.d_leaves.as<uint8_t>());
+    if (!rc) rc = stage_merkle_build(c, st, count, s.d_leaves.as<uint8_t>(), s.d_roots.as<uint8_t>(),
+                                     s.d_branches.as<uint8_t>());
+    if (rc) return rc;
+    uint8_t *o_par = s.h_out.as<uint8_t>(), *o_rt = o_par + (par_direct ? 0 : par_bytes),
+            *o_br = o_rt + (size_t)count * 32;
+    void *d_par = s.d_parity.p, *d_rt = s.d_roots.p, *d_br = s.d_branches.p;
+    auto d2h = [=](hipStream_t cs) -> int {
+        if (p > 0) {
+            if (par_direct && dpitch == parity_pitch)  // ONE linear copy: bytes [S_i, pitch) come back zero
+                RBC_HIP(hipMemcpyAsync(parity_out, d_par, par_bytes, hipMemcpyDeviceToHost, cs));
+            else if (par_direct)  // Smax bytes per row: the arena rows are zero past S_i
+                RBC_HIP(hipMemcpy2DAsync(parity_out, parity_pitch, d_par, dpitch, Smax, (size_t)count * p,
+                                         hipMemcpyDeviceToHost, cs));
+            else
+                RBC_HIP(hipMemcpyAsync(o_par, d_par, par_bytes, hipMemcpyDeviceToHost, cs));
+        }
+        RBC_HIP(hipMemcpyAsync(rt_direct ? roots_out : o_rt, d_rt, (size_t)count * 32, hipMemcpyDeviceToHost, cs));
+        if (branches_out && d > 0)
+            RBC_HIP(hipMemcpyAsync(br_direct ? branches_out : o_br, d_br, br_bytes, hipMemcpyDeviceToHost, cs));
+        return RBC_OK;
+    };
+    return submit(c, s, ticket, [=]() {
+        parallel_for(count, par_direct ? 0 : (size_t)p * Smax, [&](int i) {
+            if (!par_direct)
+                for (int j = 0; j < p; ++j)
+                    memcpy(parity_out + ((size_t)i * p + j) * parity_pitch, o_par + ((size_t)i * p + j) * dpitch, Smax);
+            if (shard_lens_out) shard_lens_out[i] = lens[count + i];
         });
         if (!rt_direct) memcpy(roots_out, o_rt, (size_t)count * 32);
         if (branches_out && d > 0 && !br_direct) memcpy(branches_out, o_br, br_out);
@@ -2304,6 +2520,30 @@ int rbc_shard(rbc_ctx *c, const uint8_t *data, size_t len, uint8_t *shards_out, 
     if (rc) return rc;
     if (shard_len_out) *shard_len_out = slen;
     return RBC_OK;
+}
+
+// shard() the way klauspost's caller sees it (rbc/rbc.go:97-100): Split's data
+// shards are slices of `data` (rbc_split_rows), Encode fills the parity rows --
+// so only those, the root and the branches come back.
+int rbc_shard_parity(rbc_ctx *c, const uint8_t *data, size_t len, uint8_t *parity_out, size_t parity_cap,
+                     size_t *shard_len_out, uint8_t *root_out, uint8_t *branches_out) {
+    if (!c || !root_out || (c->p > 0 && !parity_out)) return RBC_ERR_INVALID_ARG;
+    if (len == 0) return RBC_ERR_SHORT_DATA;
+    if (!data) return RBC_ERR_INVALID_ARG;
+    const size_t S = (len + c->k - 1) / c->k;
+    if (parity_cap < (size_t)c->p * S) return RBC_ERR_INVALID_ARG;
+    uint32_t slen = 0;
+    int rc = rbc_shard_commit_parity(c, 1, &data, &len, parity_out, S, &slen, root_out, branches_out, nullptr);
+    if (rc) return rc;
+    if (shard_len_out) *shard_len_out = slen;
+    return RBC_OK;
+}
+
+size_t rbc_split_tail_bytes(int k, size_t len) { return rbc_split_tail_bytes_impl(k, len); }
+
+int rbc_split_rows(int k, const uint8_t *data, size_t len, uint8_t *tail, size_t tail_cap, const uint8_t **rows_out,
+                   size_t *shard_len, size_t *tail_used) {
+    return rbc_split_rows_impl(k, data, len, tail, tail_cap, rows_out, shard_len, tail_used);
 }
 
 int rbc_validate_message(rbc_ctx *c, const uint8_t *root, const uint8_t *branch, size_t branch_len,

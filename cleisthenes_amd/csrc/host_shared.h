@@ -23,6 +23,39 @@ inline bool rbc_fft_supported(int n, int k) {
     return false;
 }
 
+// klauspost Split's data shards without copying whole rows (rbc/rbc.go:97-100:
+// Split returns slices of the caller's value, and allocates only where it has
+// to pad).  With S = ceil(len / k), row j is data[j*S, (j+1)*S) itself while it
+// lies wholly inside the value; the other rows live in `tail`: the row that
+// straddles len (its remaining bytes, then zeros) and the all-zero rows after it.
+inline size_t rbc_split_tail_bytes_impl(int k, size_t len) {
+    if (k <= 0 || len == 0) return 0;
+    const size_t S = (len + (size_t)k - 1) / (size_t)k;
+    return ((size_t)k - len / S) * S;
+}
+// Status values are include/rbc_gpu.h's RBC_OK (0), RBC_ERR_SHORT_DATA (-6) and
+// RBC_ERR_INVALID_ARG (-10); nothing is written unless RBC_OK is returned.
+inline int rbc_split_rows_impl(int k, const uint8_t *data, size_t len, uint8_t *tail, size_t tail_cap,
+                               const uint8_t **rows_out, size_t *shard_len, size_t *tail_used) {
+    if (k <= 0 || !rows_out) return -10;
+    if (len == 0) return -6;  // Split: len(data) == 0
+    if (!data) return -10;
+    const size_t S = (len + (size_t)k - 1) / (size_t)k;
+    const size_t full = len / S;  // rows with (j+1)*S <= len
+    const size_t need = ((size_t)k - full) * S;
+    if (need > tail_cap || (need && !tail)) return -10;
+    for (size_t j = 0; j < full; ++j) rows_out[j] = data + j * S;
+    if (need) {
+        const size_t rem = len - full * S;  // bytes of the straddling row that are data
+        for (size_t b = 0; b < rem; ++b) tail[b] = data[full * S + b];
+        for (size_t b = rem; b < need; ++b) tail[b] = 0;
+        for (size_t j = full; j < (size_t)k; ++j) rows_out[j] = tail + (j - full) * S;
+    }
+    if (shard_len) *shard_len = S;
+    if (tail_used) *tail_used = need;
+    return 0;
+}
+
 // Bytes of the pb.Message of a VAL (type 0) / ECHO (1) request for shard
 // `index` of S bytes with a depth-`depth` branch: the host mirror of the
 // marshal kernel's layout().total (wire.hip), for sizing out_pitch.

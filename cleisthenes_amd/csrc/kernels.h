@@ -7,7 +7,10 @@
 #include "../../include/rbc_gpu.h"
 #include "host_shared.h"
 
-enum { GF_MODE_ENCODE = 0, GF_MODE_DECODE = 1 };
+// GF_MODE_ENCODE_PARITY: encode whose data rows and parity rows go to two
+// buffers, data [I][k][pitch] and a dense parity arena [I][p][pitch]
+// (rbc_dev_shard_commit_parity); rs_fft only, gf_rows takes GfArgs::parity
+enum { GF_MODE_ENCODE = 0, GF_MODE_DECODE = 1, GF_MODE_ENCODE_PARITY = 2 };
 
 struct GfArgs {
     int count;                 // instances
@@ -44,6 +47,11 @@ struct GfArgs {
     int n;
     const int32_t *rcount;     // per-instance output row count (nullable -> R)
     int prio;                  // wave issue priority 0..3 (set_wave_prio)
+    // encode, optional: output row r goes to parity + inst * parity_inst_pitch +
+    // r * out_row_pitch instead of row K + r of `out`; `copy` [I][K][out_row_pitch]
+    // (out_inst_pitch = K * out_row_pitch) still receives the data rows
+    uint8_t *parity;
+    uint64_t parity_inst_pitch;
 };
 
 struct ShaArgs {
@@ -195,6 +203,11 @@ struct FftArgs {
     // bytes, zeros up to join_pitch (uniform S only, join_pitch - k*S < 256)
     uint8_t *join;
     uint32_t join_pitch;
+    // GF_MODE_ENCODE_PARITY: `shards` is the data rows [I][k][row_pitch]
+    // (inst_pitch = k * row_pitch); parity position pos is stored at
+    // parity + inst * parity_inst_pitch + (pos - k) * row_pitch
+    uint8_t *parity;           // [I][n-k][row_pitch]
+    uint64_t parity_inst_pitch;
 };
 
 // VAL / ECHO marshaling (wire.hip): message (i, j) = pb.Message bytes of

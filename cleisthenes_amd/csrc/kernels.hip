@@ -74,6 +74,9 @@ __global__ __launch_bounds__(TPB, (RC <= 21 ? 3 : 2)) void gf_rows_kernel(GfArgs
 
     const uint8_t *in_inst = a.in + (size_t)inst * a.in_inst_pitch;
     uint8_t *out_inst = a.out + (size_t)inst * a.out_inst_pitch;
+    // parity-only encode: output row r (position K + r below) is row r of the
+    // instance's block of the dense parity arena; block-uniform, SGPRs only
+    if (a.parity) out_inst = a.parity + (size_t)inst * a.parity_inst_pitch - (size_t)a.K * a.out_row_pitch;
     const rsrc_t rin = make_rsrc(in_inst, a.in_inst_bytes);
 
     if (a.mode == GF_MODE_DECODE) {
@@ -1972,6 +1975,7 @@ int rbc_gf_pick_rc(int R, int rcmax) {
 hipError_t rbc_launch_gf_rows(const GfArgs &a, hipStream_t st) {
     if (a.count <= 0 || (a.R <= 0 && !a.copy)) return hipSuccess;
     if (a.tpb != 0 && a.tpb != 256) return hipErrorInvalidValue;
+    if (a.parity && a.mode != GF_MODE_ENCODE) return hipErrorInvalidValue;  // the arena takes encode's rows K + r
     switch (a.rc) {
 #define RBC_RC_CASE(x) case x: return launch_gf_rc<x>(a, st);
         RBC_RC_CASE(1) RBC_RC_CASE(2) RBC_RC_CASE(3) RBC_RC_CASE(4) RBC_RC_CASE(5) RBC_RC_CASE(6)

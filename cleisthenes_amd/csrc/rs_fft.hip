@@ -28,7 +28,10 @@
 // rows of an already completed data half (interpolate: the missing data rows
 // are regenerated first by gf_regen_kernel) and writes the parity positions by
 // class: 0 skip (used), 1 store (missing), 2 compare (valid but unused: store,
-// flag and queue for re-hash only if the re-encoding differs).
+// flag and queue for re-hash only if the re-encoding differs).  ENCODE_PARITY
+// is ENCODE with two outputs: the data rows [I][k][pitch] and a dense parity
+// arena [I][N-k][pitch] that leaves the device in one linear copy (a Go node
+// already holds Split's data rows, rbc/rbc.go:97-100).
 #include <utility>
 
 #include "device_common.h"
@@ -297,8 +300,11 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2))) void rs
     if (a.status && a.status[inst] != 0) return;
     const uint32_t off = 4u * (uint32_t)col;
     if (off >= a.row_pitch) return;
+    // ENCODE_PARITY is ENCODE with the parity rows stored through a second
+    // descriptor (below); ENCODE and DECODE compile as before
+    constexpr bool ENC = MODE == GF_MODE_ENCODE || MODE == GF_MODE_ENCODE_PARITY;
     uint32_t S, B = 0;
-    if constexpr (MODE == GF_MODE_ENCODE) {
+    if constexpr (ENC) {
         B = a.lens ? a.lens[inst] : a.uniform_len;
         S = (B + K - 1) / K;
     } else {
@@ -314,7 +320,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2))) void rs
     auto row_load = [&](int pos) -> uint32_t { return __builtin_amdgcn_raw_buffer_load_b32(rs, (int)off, pos * pitch, 0); };
 
     uint32_t v[W];
-    if constexpr (MODE == GF_MODE_ENCODE) {
+    if constexpr (ENC) {
         const uint8_t *val = a.values + (size_t)inst * a.value_pitch;
         const auto rv = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint8_t *>(val), (short)0, (int)a.value_pitch,
                                                            0x00020000);
@@ -391,6 +397,22 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2))) void rs
             });
         };
         lch::fft<G, LOGW, 0, 0, K, K, N>(v, st);
+    } else if constexpr (MODE == GF_MODE_ENCODE_PARITY) {
+        // the data rows went to `shards` [I][K][pitch] above; parity position
+        // pos goes to row pos - K of the instance's block of the dense arena
+        // [I][N-K][pitch], through a descriptor of its own bounded to that
+        // block (SGPRs only: same lane offset, same row-offset arithmetic)
+        const auto rp = __builtin_amdgcn_make_buffer_rsrc(a.parity + (size_t)inst * a.parity_inst_pitch, (short)0,
+                                                           (N - K) * pitch, 0x00020000);
+        auto st = [&](auto Lam, auto Off, auto Lo, auto Hi) {
+            lch::sfor<decltype(Lo)::value, decltype(Hi)::value>([&](auto I) {
+                constexpr int i = decltype(I)::value, pos = decltype(Lam)::value + i;
+                if constexpr (pos >= K && pos < N)
+                    __builtin_amdgcn_raw_buffer_store_b32(v[decltype(Off)::value + i], rp, (int)off, (pos - K) * pitch,
+                                                          0);
+            });
+        };
+        lch::fft<G, LOGW, 0, 0, K, K, N>(v, st);
     } else {
         const uint32_t *cls = reinterpret_cast<const uint32_t *>(a.cls + (size_t)inst * a.cls_stride);
         // Software pipeline over output groups: the compare loads of group g
@@ -447,6 +469,8 @@ hipError_t launch_fft(const FftArgs &a, hipStream_t st) {
     dim3 grid((a.row_pitch / 4 + 63) / 64, (unsigned)a.count);
     if (a.mode == GF_MODE_ENCODE)
         hipLaunchKernelGGL((rs_fft_kernel<LOGW, K, N, GF_MODE_ENCODE>), grid, dim3(64), 0, st, a);
+    else if (a.mode == GF_MODE_ENCODE_PARITY)
+        hipLaunchKernelGGL((rs_fft_kernel<LOGW, K, N, GF_MODE_ENCODE_PARITY>), grid, dim3(64), 0, st, a);
     else
         hipLaunchKernelGGL((rs_fft_kernel<LOGW, K, N, GF_MODE_DECODE>), grid, dim3(64), 0, st, a);
     return hipGetLastError();
@@ -457,6 +481,7 @@ hipError_t launch_fft(const FftArgs &a, hipStream_t st) {
 hipError_t rbc_launch_rs_fft(const FftArgs &a, hipStream_t st) {
     if (a.count <= 0) return hipSuccess;
     if (a.row_pitch % 4) return hipErrorInvalidValue;
+    if (a.mode == GF_MODE_ENCODE_PARITY && !a.parity) return hipErrorInvalidValue;
 #define RBC_FFT_CASE(lw, kk, nn) \
     if (a.n == nn && a.k == kk) return launch_fft<lw, kk, nn>(a, st);
     RBC_FFT_GEOMS(RBC_FFT_CASE)

@@ -93,6 +93,24 @@ def _bytes_array(x) -> np.ndarray:
     return np.frombuffer(bytes(x), dtype=np.uint8)
 
 
+def split_rows(k: int, data) -> List[np.ndarray]:
+    """klauspost Split's k data shards of `data` through rbc_split_rows: each
+    row is a view of `data` where it lies wholly inside it, else a view of one
+    tail buffer (the straddling row's bytes + zeros, then all-zero rows)."""
+    d = _bytes_array(data)
+    tail = np.zeros(max(lib.rbc_split_tail_bytes(k, len(d)), 1), dtype=np.uint8)
+    rows = (c_void_p * max(k, 1))()
+    S, used = c_size_t(0), c_size_t(0)
+    check(lib.rbc_split_rows(k, _ptr(d) if len(d) else None, len(d), _ptr(tail), tail.nbytes, rows, byref(S),
+                             byref(used)), "rbc_split_rows")
+    out = []
+    for j in range(k):
+        src = d if d.ctypes.data <= rows[j] < d.ctypes.data + len(d) else tail
+        off = rows[j] - src.ctypes.data
+        out.append(src[off: off + S.value])
+    return out
+
+
 class DeviceBuffer:
     """A device allocation made by the library (hipMalloc)."""
 
@@ -375,6 +393,68 @@ class Context:
                "branches": br[:, :, : self.depth]}
         return HostTicket(self, t.value, out, keep=(arrs, vlens, vptrs, br))
 
+    # ---- parity-only shard commit (klauspost Split / Encode, rbc/rbc.go:97-100) ----
+    def split_rows(self, data) -> List[np.ndarray]:
+        """Split's k data shards of `data` (rbc_split_rows): views of `data`
+        itself for the rows that lie wholly inside it, views of one small tail
+        buffer for the padded ones.  The rows alias `data`, as klauspost's do."""
+        return split_rows(self.k, data)
+
+    def shard_parity(self, data) -> dict:
+        """rbc_shard_parity: shard(enc, data) + Merkle commit that returns only
+        the p parity shards -> {parity, shard_len, root, branches (flat, Go form,
+        all N)}; the data shards are split_rows(data)."""
+        d = _bytes_array(data)
+        S = (len(d) + self.k - 1) // self.k if len(d) else 0
+        out = np.zeros(max(self.p * S, 1), dtype=np.uint8)
+        br = np.zeros(max(self.n * self.depth * 32, 1), dtype=np.uint8)
+        root = np.zeros(32, dtype=np.uint8)
+        slen = c_size_t(0)
+        check(lib.rbc_shard_parity(self._p, _ptr(d) if len(d) else None, len(d), _ptr(out), self.p * S, byref(slen),
+                                   _ptr(root), _ptr(br)), "rbc_shard_parity")
+        S = slen.value
+        brs = br[: self.n * self.depth * 32].reshape(self.n, self.depth, 32) if self.depth else None
+        flat = [b"".join(bytes(brs[j, lvl]) for lvl in range(self.depth) if not (lvl == 0 and (j ^ 1) >= self.n))
+                for j in range(self.n)]
+        return {"parity": [out[r * S:(r + 1) * S].copy() for r in range(self.p)], "shard_len": S,
+                "root": bytes(root), "branches": flat}
+
+    def shard_commit_parity_batch(self, values: Sequence[bytes]) -> dict:
+        return self.shard_commit_parity_submit(values).wait()
+
+    def shard_commit_parity_submit(self, values: Sequence[bytes], out: Optional[dict] = None) -> "HostTicket":
+        """Asynchronous rbc_shard_commit_parity (see shard_commit_submit): the
+        result holds "parity" [count][p][pitch] (row r = shard k + r), "shard_lens",
+        "roots" and "branches", and no data rows.  `out` may hold preallocated
+        (e.g. pinned_empty) "parity" [count][p][pitch >= Smax] (a 64-B pitch: one
+        linear D2H copy), "roots" [count][32] and "branches"
+        [count][N][max(d,1)][32] arrays."""
+        count = len(values)
+        arrs = [v if isinstance(v, np.ndarray) and v.dtype == np.uint8 and v.flags.c_contiguous
+                else _bytes_array(v) for v in values]
+        Smax = max((len(a) + self.k - 1) // self.k for a in arrs)
+        pitch = Smax
+        bshape = (count, self.n, max(self.depth, 1), 32)
+        if out is not None:
+            parity, roots, br = out["parity"], out["roots"], out["branches"]
+            pitch = parity.shape[2]
+            assert parity.shape[:2] == (count, self.p) and pitch >= Smax and parity.flags.c_contiguous
+            assert roots.shape == (count, 32) and br.shape == bshape
+        else:
+            parity = np.zeros((count, self.p, pitch), dtype=np.uint8)
+            roots = np.zeros((count, 32), dtype=np.uint8)
+            br = np.zeros(bshape, dtype=np.uint8)
+        slens = np.zeros(count, dtype=np.uint32)
+        vlens = (c_size_t * count)(*[len(a) for a in arrs])
+        vptrs = (c_void_p * count)(*[a.ctypes.data if len(a) else None for a in arrs])
+        t = c_uint64(0)
+        check(lib.rbc_shard_commit_parity(self._p, count, vptrs, vlens, _ptr(parity) if self.p else None, pitch,
+                                          slens.ctypes.data_as(_lib.u32p), _ptr(roots), _ptr(br), byref(t)),
+              "rbc_shard_commit_parity")
+        res = {"parity": parity[:, :, :Smax] if pitch != Smax else parity, "shard_lens": slens, "roots": roots,
+               "branches": br[:, :, : self.depth]}
+        return HostTicket(self, t.value, res, keep=(arrs, vlens, vptrs, br, parity))
+
     def shard_commit_val(self, values: Sequence[bytes], ring: Optional[np.ndarray] = None) -> dict:
         """rbc_shard_commit_val: shard + commit and the N per-recipient VAL
         pb.Messages of every proposal, handed over in one D2H.  `ring` may be
@@ -587,6 +667,14 @@ class Context:
         check(lib.rbc_dev_shard_commit(self._p, _dv(stream), count, _dv(values), value_pitch, _dv(value_lens),
                                        uniform_len, _dv(shards), shard_pitch, _dv(shard_lens), _dv(leaves),
                                        _dv(roots), _dv(branches)), "rbc_dev_shard_commit")
+
+    def dev_shard_commit_parity(self, stream, count, values, value_pitch, value_lens, uniform_len, data_rows, parity,
+                                row_pitch, shard_lens, leaves, roots, branches):
+        """rbc_dev_shard_commit_parity: data rows [count][k][row_pitch] and the
+        dense parity arena [count][p][row_pitch] instead of [count][n][pitch]."""
+        check(lib.rbc_dev_shard_commit_parity(self._p, _dv(stream), count, _dv(values), value_pitch, _dv(value_lens),
+                                              uniform_len, _dv(data_rows), _dv(parity), row_pitch, _dv(shard_lens),
+                                              _dv(leaves), _dv(roots), _dv(branches)), "rbc_dev_shard_commit_parity")
 
     def dev_verify(self, stream, count, shards, shard_pitch, shard_lens, uniform_len, branches, roots, present,
                    valid, leaves):

@@ -7,6 +7,7 @@
  * hold are served from here through a thin cgo shim:
  *
  *   rbc/rbc.go:97-100  shard(enc, data) ([][]byte, error)     -> rbc_shard / rbc_shard_commit
+ *                      (parity rows only, data shards as slices) -> rbc_shard_parity / rbc_shard_commit_parity
  *   rbc/rbc.go:92-95   validateMessage(echo *EchoRequest) bool -> rbc_validate_message / rbc_validate_batch
  *   rbc/rbc.go:86-90   interpolate(rootHash, shards) ([]byte, error)
  *                                                             -> rbc_interpolate / rbc_interpolate_batch
@@ -45,6 +46,10 @@ extern "C" {
 #endif
 
 #define RBC_ABI_VERSION 7
+/* Additions within ABI 7, detected by symbol presence: the parity-only shard
+ * commit (rbc_dev_shard_commit_parity, rbc_shard_commit_parity,
+ * rbc_shard_parity, rbc_split_rows, rbc_split_tail_bytes). */
+#define RBC_HAS_SHARD_COMMIT_PARITY 1
 
 /* ---- status codes ------------------------------------------------------- */
 #define RBC_OK 0
@@ -171,6 +176,19 @@ int rbc_dev_shard_commit(rbc_ctx *ctx, void *stream, int count, const uint8_t *v
                          const uint32_t *value_lens, uint32_t uniform_value_len, uint8_t *shards,
                          uint32_t shard_pitch, const uint32_t *shard_lens, uint8_t *leaves, uint8_t *roots,
                          uint8_t *branches);
+/* rbc_dev_shard_commit for a caller that needs only what klauspost's Encode
+ * computes (rbc/rbc.go:97-100: Split returns the k data shards as slices of
+ * the caller's value, Encode fills the p = n-k parity rows): the data rows go
+ * to data_rows [count][k][row_pitch] (they are hashed, and a device pipeline
+ * may use them), the parity rows to the dense arena parity
+ * [count][p][row_pitch] -- one linear copy away from the host.  leaves, roots
+ * and branches as rbc_dev_shard_commit ([count][n][32], leaf j of the data
+ * row j < k or of arena row j - k).  Pitch and argument rules are
+ * rbc_dev_shard_commit's; parity may be NULL when p == 0. */
+int rbc_dev_shard_commit_parity(rbc_ctx *ctx, void *stream, int count, const uint8_t *values, uint64_t value_pitch,
+                                const uint32_t *value_lens, uint32_t uniform_value_len, uint8_t *data_rows,
+                                uint8_t *parity, uint32_t row_pitch, const uint32_t *shard_lens, uint8_t *leaves,
+                                uint8_t *roots, uint8_t *branches);
 /* ECHO-side validateMessage for every received (instance, shard j): hash
  * shard j, walk branch j, compare with roots[i].  valid[i][j] = present[i][j]
  * && ok (present nullable = all).  Only present shards are hashed (they are
@@ -285,6 +303,21 @@ int rbc_dev_inject_faults(rbc_ctx *ctx, void *stream, int count, uint8_t *shards
 int rbc_shard_commit(rbc_ctx *ctx, int count, const uint8_t *const *values, const size_t *value_lens,
                      uint8_t *shards_out, size_t shard_pitch, uint32_t *shard_lens_out, uint8_t *roots_out,
                      uint8_t *branches_out, uint64_t *ticket);
+/* rbc_shard_commit that returns only the p = n-k parity rows: klauspost's
+ * Split hands the caller the k data shards as slices of its own value and
+ * Encode fills the parity (rbc/rbc.go:97-100), so a Go node already holds the
+ * data rows (rbc_split_rows) and the GPU owes it parity, roots and branches.
+ * parity_out [count][p][parity_pitch], row r = shard k + r (S_i bytes used).
+ * Staging rules are rbc_shard_commit's: pinned parity_out with parity_pitch %
+ * 64 == 0 comes back in ONE linear copy of count*p*parity_pitch bytes, bytes
+ * [S_i, parity_pitch) as zero; pinned output at another pitch receives Smax
+ * bytes per row; pageable output goes through pinned staging.  Same
+ * RBC_ERR_SHORT_DATA / RBC_ERR_INVALID_ARG checks (parity_pitch < Smax
+ * included), all made before any device work.  With p == 0 only roots and
+ * branches are returned (parity_out may be NULL). */
+int rbc_shard_commit_parity(rbc_ctx *ctx, int count, const uint8_t *const *values, const size_t *value_lens,
+                            uint8_t *parity_out, size_t parity_pitch, uint32_t *shard_lens_out, uint8_t *roots_out,
+                            uint8_t *branches_out, uint64_t *ticket);
 /* validateMessage for `count` independent ECHO messages: shard i
  * (shard_lens[i] bytes), leaf index indices[i], flat branch (branch_lens[i]
  * bytes, Go form), root (32 bytes).  ok_out[i] = 1 valid / 0 invalid. */
@@ -384,6 +417,26 @@ int rbc_poll(rbc_ctx *ctx, uint64_t ticket, int *done);
  * *shard_len_out = S, root_out 32 B, branches_out n*d*32 B (nullable). */
 int rbc_shard(rbc_ctx *ctx, const uint8_t *data, size_t len, uint8_t *shards_out, size_t shards_cap,
               size_t *shard_len_out, uint8_t *root_out, uint8_t *branches_out);
+/* shard(enc, data) + commit as klauspost's caller holds it (rbc/rbc.go:97-100,
+ * Split / Encode): the data shards stay slices of `data` (rbc_split_rows), and
+ * only the parity comes back -- parity_out p*S bytes (shard k + r at r*S,
+ * parity_cap >= p*S), *shard_len_out = S, root_out 32 B, branches_out n*d*32 B
+ * (nullable). */
+int rbc_shard_parity(rbc_ctx *ctx, const uint8_t *data, size_t len, uint8_t *parity_out, size_t parity_cap,
+                     size_t *shard_len_out, uint8_t *root_out, uint8_t *branches_out);
+/* klauspost Split's data shards (rbc/rbc.go:97-100) without copying whole
+ * rows; host code only, no context.  With S = ceil(len / k), rows_out[j] =
+ * data + j*S while (j+1)*S <= len; the other rows point into `tail`, which
+ * receives the straddling row's remaining bytes followed by zeros (rows wholly
+ * past len are all zero).  The tail needs rbc_split_tail_bytes(k, len) =
+ * (k - len/S) * S bytes (tail may be NULL when that is 0); *shard_len = S,
+ * *tail_used = the bytes written (both nullable).  The returned rows alias
+ * `data`, as klauspost's do.  RBC_ERR_SHORT_DATA for len == 0,
+ * RBC_ERR_INVALID_ARG for k <= 0, NULL data / rows_out or a tail_cap that is
+ * too small; nothing is written on error. */
+size_t rbc_split_tail_bytes(int k, size_t len);
+int rbc_split_rows(int k, const uint8_t *data, size_t len, uint8_t *tail, size_t tail_cap, const uint8_t **rows_out,
+                   size_t *shard_len, size_t *tail_used);
 /* validateMessage(echo): *ok = 1 iff the branch proves shard at `index` under root. */
 int rbc_validate_message(rbc_ctx *ctx, const uint8_t *root, const uint8_t *branch, size_t branch_len,
                          const uint8_t *shard, size_t shard_len, uint32_t index, int *ok);
