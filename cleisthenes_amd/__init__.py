@@ -15,10 +15,11 @@ from .rbc import (  # noqa: F401
     RBCError,
     Stream,
     Event,
+    WireRx,
     device_count,
     pinned_empty,
     split_rows,
 )
 
-__all__ = ["Batcher", "Context", "DeviceBuffer", "Encoder", "RBCError", "Stream", "Event", "device_count", "pinned_empty",
-           "split_rows"]
+__all__ = ["Batcher", "Context", "DeviceBuffer", "Encoder", "RBCError", "Stream", "Event", "WireRx", "device_count",
+           "pinned_empty", "split_rows"]

@@ -180,6 +180,15 @@ _SIGS = {
     "rbc_val_message_size": (c_size_t, [c_int, c_uint32, c_uint32, c_int]),
     "rbc_shard_commit_val": (c_int, [c_void_p, c_int, c_void_p, szp, c_void_p, c_size_t, u32p, c_void_p,
                                      POINTER(c_uint64)]),
+    # the wire receive path (RBC_HAS_WIRE_RX)
+    "rbc_dev_unmarshal_val": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                      c_uint32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "rbc_wire_rx_create": (c_int, [c_void_p, c_int, c_size_t, c_uint32, POINTER(c_void_p)]),
+    "rbc_wire_rx_destroy": (None, [c_void_p]),
+    "rbc_wire_validate": (c_int, [c_void_p, c_int, c_void_p, c_size_t, c_void_p, c_void_p, c_void_p, c_void_p,
+                                  c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, POINTER(c_uint64)]),
+    "rbc_wire_wait": (c_int, [c_void_p, c_uint64]),
+    "rbc_wire_poll": (c_int, [c_void_p, c_uint64, POINTER(c_int)]),
     # parity-only shard commit (RBC_HAS_SHARD_COMMIT_PARITY)
     "rbc_dev_shard_commit_parity": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_uint64, c_void_p, c_uint32,
                                             c_void_p, c_void_p, c_uint32, c_void_p, c_void_p, c_void_p, c_void_p]),
@@ -198,10 +207,24 @@ _SIGS = {
     "rbc_node_stats": (c_int, [c_void_p, POINTER(c_int), POINTER(c_int), POINTER(c_int), POINTER(c_int)]),
 }
 
+# Additions made at an unchanged ABI version are detected by symbol, as their
+# header macros say (RBC_HAS_WIRE_RX): another build of ABI 7 (RBC_GPU_LIB)
+# may lack them.  They are then left unbound, and using one raises.
+_BY_SYMBOL = ("rbc_dev_unmarshal_val", "rbc_wire_rx_create", "rbc_wire_rx_destroy", "rbc_wire_validate",
+              "rbc_wire_wait", "rbc_wire_poll")
+HAS_WIRE_RX = all(hasattr(lib, _name) for _name in _BY_SYMBOL)
+
 for _name, (_res, _args) in _SIGS.items():
+    if _name in _BY_SYMBOL and not HAS_WIRE_RX:
+        continue
     _fn = getattr(lib, _name)
     _fn.restype = _res
     _fn.argtypes = _args
+
+
+def require_wire_rx() -> None:
+    if not HAS_WIRE_RX:
+        raise ImportError(f"{LIB_PATH} has no wire receive path (RBC_HAS_WIRE_RX): rbc_dev_unmarshal_val missing")
 
 
 def header_functions(path: str = None):
@@ -236,6 +259,8 @@ RBC_ERR_PROTOCOL = -20  # include/rbc_protocol.h
 
 # pb.RBC type (pb/message.proto:30-34)
 RBC_MSG_VAL, RBC_MSG_ECHO, RBC_MSG_READY = 0, 1, 2
+# rbc_dev_unmarshal_val status (include/rbc_protocol.h)
+RBC_WIRE_OK, RBC_WIRE_FALLBACK = 0, 1
 
 
 class RBCError(Exception):

@@ -227,6 +227,31 @@ struct WireArgs {
 };
 hipError_t rbc_launch_marshal_val(const WireArgs &a, hipStream_t st);
 
+// Per-message status of the unmarshal kernel (include/rbc_protocol.h)
+enum { WIRE_OK = 0, WIRE_FALLBACK = 1 };
+
+// VAL / ECHO unmarshaling (wire.hip), the inverse: message i is the bytes
+// msgs[offs[i], offs[i] + lens[i]) from the node at Merkle leaf idx[i].  A
+// canonical message (byte-for-byte what marshal_val_kernel writes) has its
+// fields decoded to the device forms; every other one only gets status
+// WIRE_FALLBACK.  The kernel reads msgs[offs[i], offs[i] + round_up(lens[i], 16))
+// at most and writes nothing outside message i's own output slots.
+struct WireRxArgs {
+    int count, n, depth;
+    const uint8_t *msgs;
+    const uint64_t *offs;  // % 16 == 0
+    const uint32_t *lens;
+    const uint8_t *idx;    // sender's leaf index
+    uint8_t *rows;         // shard i at rows + i*row_pitch, zeros up to round_up(S, 64)
+    uint32_t row_pitch;    // % 64 == 0
+    uint32_t *shard_lens;  // [count] (0 for a fallback message)
+    uint8_t *branches;     // [count][max(depth,1)][32], device form
+    uint8_t *roots;        // [count][32]
+    uint8_t *types;        // [count]
+    int32_t *status;       // [count] WIRE_OK / WIRE_FALLBACK
+};
+hipError_t rbc_launch_unmarshal_val(const WireRxArgs &a, hipStream_t st);
+
 hipError_t rbc_launch_rs_fft(const FftArgs &a, hipStream_t st);
 
 int rbc_gf_pick_rc(int R, int rcmax);

@@ -17,6 +17,10 @@
 // funnel shift), 5 base64 groups as packed sextets, SWAR ASCII mapping, one
 // funnel shift to the chunk's phase and one 16-byte store.  The few chunks
 // that straddle a header, a JSON literal or a run's end take a per-byte path.
+//
+// The receive side (unmarshal_val_kernel, below the marshal kernel) is the
+// inverse: canonical messages decoded back into the device forms, everything
+// else left to the host decoder.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -212,7 +216,221 @@ __global__ __launch_bounds__(256) void marshal_val_kernel(WireArgs a) {
     if (lane == 0 && a.out_lens) a.out_lens[msg] = L.total;
 }
 
+// ---------------------------------------------------------------------------
+// The receive side: unmarshal_val_kernel, the inverse of marshal_val_kernel.
+//
+// A message is decoded only when it is canonical, i.e. byte-for-byte what the
+// kernel above writes for some (root, branch, shard, type).  Its shape then
+// follows from its length and the sender's leaf alone: the branch length from
+// (idx, n, depth), the block's base64 length from the total, S from that and
+// the block's trailing '=' count.  So the wave derives a Layout from lens[i],
+// never from a byte of the message, and then checks every byte against it:
+// header and literals against msg_byte(), every base64 character against the
+// alphabet, '=' only where b64_len() pads.  Anything else is WIRE_FALLBACK,
+// the host decoder's business.  Like Go's non-strict decoder (and
+// b64_decode_range, rbc_node.cpp) the non-zero trailing bits of a last quantum
+// are ignored.
+//
+// Output-centric like the send side: a lane-step produces one aligned 16-byte
+// chunk of decoded bytes with one store.  A chunk wholly inside full groups
+// reads its 24 characters as 7 dwords and one funnel shift each, maps ASCII to
+// sextets with SWAR range arithmetic (which yields the invalid-character mask),
+// packs each group with shift-or and a byte permute, and funnel-shifts the 18
+// bytes to the chunk's phase.  The chunks at a run's end go byte by byte.
+// ---------------------------------------------------------------------------
+
+// The Layout of a canonical message of `total` bytes with a br_len-byte
+// branch, if there is one (L.S is then the unpadded 3 * groups), from
+// layout() alone: total = overhead + 4 * groups, where the overhead grows by
+// at most 8 (two varints) over that of a one-group message.
+__device__ bool rx_layout(uint32_t total, uint32_t br_len, Layout &L, int &type) {
+    if (total > 0x7fffffffu) return false;
+    for (int t = 0; t < 2; ++t) {
+        const uint32_t t1 = layout(3, br_len, t).total;
+        if (total < t1) continue;
+        const uint32_t G = 1 + ((total - t1) >> 2);
+        for (uint32_t d = 0; d < 4 && d < G; ++d) {
+            const Layout c = layout(3 * (G - d), br_len, t);
+            if (c.total == total) {
+                L = c;
+                type = t;
+                return true;
+            }
+        }
+    }
+    return false;
+}
+
+// alphabet value of one character, -1 outside the standard alphabet
+__device__ __forceinline__ int b64_val(uint32_t c) {
+    return c - 'A' < 26u ? (int)(c - 'A')
+           : c - 'a' < 26u ? (int)(c - 'a' + 26)
+           : c - '0' < 10u ? (int)(c - '0' + 52)
+           : c == '+' ? 62
+           : c == '/' ? 63
+                      : -1;
+}
+
+// 4 base64 characters -> their sextets, byte for byte; bad gets 0x80 in every
+// byte that is outside the alphabet
+__device__ __forceinline__ uint32_t b64_sextets4(uint32_t x, uint32_t &bad) {
+    const uint32_t c = x & 0x7f7f7f7fu;  // 7-bit bytes: the range adds below never carry across
+#define RBC_GE(k) ((c + (0x80u - (uint32_t)(k)) * 0x01010101u) & 0x80808080u)
+    const uint32_t up = RBC_GE('A') & ~RBC_GE('Z' + 1), lo = RBC_GE('a') & ~RBC_GE('z' + 1);
+    const uint32_t dg = RBC_GE('0') & ~RBC_GE('9' + 1), pl = RBC_GE('+') & ~RBC_GE('+' + 1);
+    const uint32_t sl = RBC_GE('/') & ~RBC_GE('/' + 1);
+#undef RBC_GE
+    bad |= (x | ~(up | lo | dg | pl | sl)) & 0x80808080u;
+    // value = c + offset (mod 64): 'A' -> 0, 'a' -> 26, '0' -> 52, '+' -> 62, '/' -> 63
+    const uint32_t off = (up >> 7) * 63u + (lo >> 7) * 57u + (dg >> 7) * 4u + (pl >> 7) * 19u + (sl >> 7) * 16u;
+    return (c + off) & 0x3f3f3f3fu;
+}
+
+// 4 sextets (first in the lowest byte) -> the group's 3 bytes, first in the lowest byte
+__device__ __forceinline__ uint32_t b64_bytes3(uint32_t v) {
+    const uint32_t w = ((v & 0x3fu) << 18) | ((v & 0x3f00u) << 4) | ((v >> 10) & 0xfc0u) | (v >> 24);
+    return __builtin_amdgcn_perm(0u, w, 0x0c000102u);
+}
+
+// Fast path: decoded bytes [o0, o0 + 16) of the base64 run at message offset
+// off, from the 6 full groups (24 characters) that hold them.  Reads the 7
+// dwords from the one that holds the first character on.
+__device__ __forceinline__ uint4 unb64_chunk16(const uint8_t *m, uint32_t off, uint32_t o0, uint32_t &bad) {
+    const uint32_t g0 = o0 / 3, e = o0 - 3 * g0, P = off + 4 * g0, al = P & 3;
+    const uint32_t *s32 = reinterpret_cast<const uint32_t *>(m) + (P >> 2);
+    const uint32_t d0 = s32[0], d1 = s32[1], d2 = s32[2], d3 = s32[3], d4 = s32[4], d5 = s32[5], d6 = s32[6];
+    const uint32_t t0 = b64_bytes3(b64_sextets4(__builtin_amdgcn_alignbyte(d1, d0, al), bad));
+    const uint32_t t1 = b64_bytes3(b64_sextets4(__builtin_amdgcn_alignbyte(d2, d1, al), bad));
+    const uint32_t t2 = b64_bytes3(b64_sextets4(__builtin_amdgcn_alignbyte(d3, d2, al), bad));
+    const uint32_t t3 = b64_bytes3(b64_sextets4(__builtin_amdgcn_alignbyte(d4, d3, al), bad));
+    const uint32_t t4 = b64_bytes3(b64_sextets4(__builtin_amdgcn_alignbyte(d5, d4, al), bad));
+    const uint32_t t5 = b64_bytes3(b64_sextets4(__builtin_amdgcn_alignbyte(d6, d5, al), bad));
+    // the 18 bytes as dwords, then bytes e .. e+15 of them
+    const uint32_t D0 = t0 | t1 << 24, D1 = t1 >> 8 | t2 << 16, D2 = t2 >> 16 | t3 << 8, D3 = t4 | t5 << 24;
+    const uint32_t D4 = t5 >> 8;
+    return make_uint4(__builtin_amdgcn_alignbyte(D1, D0, e), __builtin_amdgcn_alignbyte(D2, D1, e),
+                      __builtin_amdgcn_alignbyte(D3, D2, e), __builtin_amdgcn_alignbyte(D4, D3, e));
+}
+
+// Slow path: decoded bytes [o0, o0 + 16) of the run of len bytes, zeros from
+// len on; checks all four characters of every group it takes a byte from
+// (alphabet, and '=' exactly on the padding positions of the last group).
+__device__ uint4 unb64_chunk_slow(const uint8_t *m, uint32_t off, uint32_t len, uint32_t o0, uint32_t &bad) {
+    const uint32_t ng = (len + 2) / 3, pad = 3 * ng - len;
+    uint32_t d[4] = {0, 0, 0, 0};
+#pragma unroll
+    for (int b = 0; b < 16; ++b) {
+        const uint32_t o = o0 + b;
+        if (o < len) {
+            const uint32_t g = o / 3, r = o - 3 * g;
+            const uint32_t np = (g == ng - 1) ? pad : 0u;
+            const uint8_t *c = m + off + 4 * g;
+            uint32_t w = 0;
+#pragma unroll
+            for (uint32_t q = 0; q < 4; ++q) {
+                const uint32_t ch = c[q];
+                int v = 0;
+                if (q + np >= 4) {
+                    if (ch != '=') bad |= 1u;
+                } else if ((v = b64_val(ch)) < 0) {
+                    bad |= 1u;
+                    v = 0;
+                }
+                w = w << 6 | (uint32_t)v;
+            }
+            d[b >> 2] |= ((w >> (16 - 8 * r)) & 0xffu) << (8 * (b & 3));
+        }
+    }
+    return make_uint4(d[0], d[1], d[2], d[3]);
+}
+
+// one wave per message; 4 waves (messages) per block
+__global__ __launch_bounds__(256) void unmarshal_val_kernel(WireRxArgs a) {
+    const uint32_t i = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (i >= (uint32_t)a.count) return;
+    const uint32_t lane = threadIdx.x & 63;
+    const uint32_t total = a.lens[i], j = a.idx[i];
+    const uint8_t *m = a.msgs + a.offs[i];
+    const bool empty0 = a.depth > 0 && (int)(j ^ 1u) >= a.n;
+    const uint32_t br_len = 32u * (a.depth - (empty0 ? 1 : 0));
+    // the shape, from the length and the leaf alone (wave-uniform)
+    Layout L;
+    int type = 0;
+    bool shaped = j < (uint32_t)a.n && rx_layout(total, br_len, L, type);
+    uint32_t S = 0;
+    if (shaped) {
+        // every offset is inside [0, total): the padding count is the only thing read so far
+        const uint32_t pad = m[L.end_lit_off - 1] == '=' ? (m[L.end_lit_off - 2] == '=' ? 2u : 1u) : 0u;
+        S = L.S - pad;
+        shaped = S <= a.row_pitch;
+    }
+    if (!shaped) {
+        if (lane == 0) {
+            a.status[i] = WIRE_FALLBACK;
+            a.types[i] = 0;
+            a.shard_lens[i] = 0;
+        }
+        return;
+    }
+    L.S = S;
+    uint32_t bad = 0;
+    // header, JSON literals and type field: at most 12 + 13 + 26 + 3 + 2 bytes, one per lane
+    {
+        const uint32_t head = L.hdr + 13, mid = br_len ? 24u : 26u;
+        const uint32_t nn = head + mid + 3 + (type ? 2u : 0u);
+        if (lane < nn) {
+            uint32_t p;
+            if (lane < head) {
+                p = lane;
+            } else {
+                const uint32_t k = lane - head;
+                if (k >= mid) p = L.end_lit_off + (k - mid);  // '"]}' and the type field behind it
+                else if (br_len && k >= 12) p = L.blk_lit_off + (k - 12);
+                else p = L.br_lit_off + k;
+            }
+            if (m[p] != msg_byte(L, p, type, nullptr, nullptr, nullptr)) bad = 1;
+        }
+    }
+    // the three base64 runs, one 16-byte chunk of decoded bytes per lane-step
+    const uint32_t nblk = ((S + 63u) & ~63u) >> 4, nbr = br_len >> 4, nq = nblk + nbr + 2;
+    uint8_t *slot = a.branches + (size_t)i * (a.depth > 1 ? a.depth : 1) * 32u;
+    for (uint32_t q = lane; q < nq; q += 64) {
+        uint32_t off, len, o0;
+        uint8_t *dst;
+        if (q < nblk) {
+            off = L.blk_off, len = S, o0 = q << 4;
+            dst = a.rows + (size_t)i * a.row_pitch;
+        } else if (q < nblk + nbr) {
+            off = L.br_off, len = br_len, o0 = (q - nblk) << 4;
+            dst = slot + (empty0 ? 32u : 0u);
+        } else {
+            off = L.root_off, len = 32, o0 = (q - nblk - nbr) << 4;
+            dst = a.roots + (size_t)i * 32;
+        }
+        uint4 v = make_uint4(0, 0, 0, 0);
+        if (o0 < len) {
+            if (4 * (o0 / 3) + 24 <= len / 3 * 4) v = unb64_chunk16(m, off, o0, bad);
+            else v = unb64_chunk_slow(m, off, len, o0, bad);
+        }
+        *reinterpret_cast<uint4 *>(dst + o0) = v;
+    }
+    // the zero slot of an empty level-0 sibling (or of a depth-0 tree)
+    if ((empty0 || a.depth == 0) && lane < 2) reinterpret_cast<uint4 *>(slot)[lane] = make_uint4(0, 0, 0, 0);
+    const bool fail = __any(bad != 0);
+    if (lane == 0) {
+        a.status[i] = fail ? WIRE_FALLBACK : WIRE_OK;
+        a.types[i] = (uint8_t)type;
+        a.shard_lens[i] = fail ? 0u : S;
+    }
+}
+
 }  // namespace
+
+hipError_t rbc_launch_unmarshal_val(const WireRxArgs &a, hipStream_t st) {
+    if (a.count <= 0) return hipSuccess;
+    hipLaunchKernelGGL(unmarshal_val_kernel, dim3(((unsigned)a.count + 3) / 4), dim3(256), 0, st, a);
+    return hipGetLastError();
+}
 
 hipError_t rbc_launch_marshal_val(const WireArgs &a, hipStream_t st) {
     const uint64_t msgs = (uint64_t)a.count * a.n;

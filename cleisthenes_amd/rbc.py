@@ -726,6 +726,15 @@ class Context:
                                       _dv(shard_lens), uniform_len, _dv(branches), _dv(roots), _dv(out), out_pitch,
                                       _dv(out_lens)), "rbc_dev_marshal_val")
 
+    def dev_unmarshal_val(self, stream, count, msgs, offs, lens, idx, rows, row_pitch, shard_lens_out, branches_out,
+                          roots_out, types_out, status_out):
+        """Received VAL / ECHO pb.Message bytes decoded in HBM (include/rbc_protocol.h):
+        status 0 = decoded, 1 = not canonical, leave it to the host decoder."""
+        _lib.require_wire_rx()
+        check(lib.rbc_dev_unmarshal_val(self._p, _dv(stream), count, _dv(msgs), _dv(offs), _dv(lens), _dv(idx),
+                                        _dv(rows), row_pitch, _dv(shard_lens_out), _dv(branches_out), _dv(roots_out),
+                                        _dv(types_out), _dv(status_out)), "rbc_dev_unmarshal_val")
+
     def val_message_size(self, shard_len: int, index: int = 0, msg_type: int = 0) -> int:
         return lib.rbc_val_message_size(self.n, shard_len, index, msg_type)
 
@@ -767,6 +776,66 @@ class Context:
         if with_comm:
             out.update(nranks=nr.value, rank=rk.value)
         return out
+
+
+class WireRx:
+    """rbc_wire_rx (include/rbc_protocol.h): ECHOs validated straight from
+    their wire bytes, the shards kept on the device."""
+
+    def __init__(self, ctx: Context, max_msgs: int, max_ring_bytes: int, row_pitch: int):
+        _lib.require_wire_rx()
+        p = c_void_p()
+        check(lib.rbc_wire_rx_create(ctx._p, max_msgs, max_ring_bytes, row_pitch, byref(p)), "rbc_wire_rx_create")
+        self._p, self.ctx, self.row_pitch = p, ctx, row_pitch
+
+    def close(self) -> None:
+        if getattr(self, "_p", None):
+            lib.rbc_wire_rx_destroy(self._p)
+            self._p = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def validate(self, ring: np.ndarray, offs, lens, idx, keep: DeviceBuffer, ring_bytes: Optional[int] = None) -> dict:
+        return self.validate_submit(ring, offs, lens, idx, keep, ring_bytes).wait()
+
+    def validate_submit(self, ring: np.ndarray, offs, lens, idx, keep: DeviceBuffer,
+                        ring_bytes: Optional[int] = None) -> "HostTicket":
+        """Asynchronous rbc_wire_validate: message i is ring[offs[i] : offs[i] +
+        lens[i]] (offs[i] % 16 == 0) from the member at leaf idx[i]; its shard
+        stays at keep.value + i*row_pitch.  .wait() returns verdict (1 valid,
+        0 proof fails, 2 fallback to the host decoder), types, roots [count][32],
+        shard_lens and leaves [count][32]."""
+        count = len(offs)
+        assert isinstance(ring, np.ndarray) and ring.dtype == np.uint8 and ring.flags.c_contiguous
+        o = np.ascontiguousarray(offs, dtype=np.uint64)
+        ln = np.ascontiguousarray(lens, dtype=np.uint32)
+        ix = np.ascontiguousarray(idx, dtype=np.uint8)
+        m = max(count, 1)
+        out = {"verdict": np.zeros(m, np.uint8), "types": np.zeros(m, np.uint8), "roots": np.zeros((m, 32), np.uint8),
+               "shard_lens": np.zeros(m, np.uint32), "leaves": np.zeros((m, 32), np.uint8)}
+        t = c_uint64(0)
+        check(lib.rbc_wire_validate(self._p, count, _ptr(ring), ring.nbytes if ring_bytes is None else ring_bytes,
+                                    _ptr(o), _ptr(ln), _ptr(ix), _ptr(out["verdict"]), _ptr(out["types"]),
+                                    _ptr(out["roots"]), _ptr(out["shard_lens"]), _ptr(out["leaves"]), keep.ptr,
+                                    keep.nbytes, byref(t)), "rbc_wire_validate")
+        rx = self
+
+        class _W(HostTicket):
+            def done(self_) -> bool:
+                d = c_int(0)
+                check(lib.rbc_wire_poll(rx._p, self_.ticket, byref(d)), "rbc_wire_poll")
+                return bool(d.value)
+
+            def wait(self_) -> dict:
+                if self_._keep is not None:
+                    check(lib.rbc_wire_wait(rx._p, self_.ticket), "rbc_wire_wait")
+                    self_._keep = None
+                return {k: v[:count] for k, v in out.items()}
+        return _W(self.ctx, t.value, None, keep=(ring, o, ln, ix, out, keep))
 
 
 class Encoder:

@@ -94,6 +94,71 @@ int rbc_shard_commit_val(rbc_ctx *ctx, int count, const uint8_t *const *values, 
                          uint8_t *msgs, size_t msg_pitch, uint32_t *msg_lens, uint8_t *roots_out,
                          uint64_t *ticket);
 
+/* ---- device-side unmarshaling (the receive path of VAL / ECHO) ------------
+ * The mirror of rbc_dev_marshal_val, present when RBC_HAS_WIRE_RX is defined
+ * (the ABI version stays 7: detect the addition by symbol).  Message i is the
+ * raw pb.Message bytes msgs[offs[i], offs[i] + lens[i]) as a pass-through gRPC
+ * codec hands them over, sent by the member at Merkle leaf idx[i].
+ * offs[i] % 16 == 0 and the arena holds round_up(lens[i], 16) bytes from
+ * offs[i]: the kernel reads no byte outside that range, whatever the message
+ * says.
+ *
+ * A message is decoded when it is canonical: byte-for-byte what
+ * rbc_pb_encode_rbc(type, rbc_json_encode_val(root, branch, block)) emits for
+ * a 32-byte root, the flat branch of leaf idx[i] (32 bytes per non-empty
+ * level), one block of 1..row_pitch bytes and type VAL or ECHO.  Then
+ * status_out[i] = RBC_WIRE_OK and types_out[i], roots_out[i][32],
+ * branches_out[i][max(depth,1)][32] (the rbc_dev_* form: a zero slot for an
+ * empty level-0 sibling), shard_lens_out[i] = S and the shard at
+ * rows + i*row_pitch (zeros from S to round_up(S, 64)) equal what
+ * rbc_pb_decode_rbc + rbc_json_decode_val return for the same bytes.
+ * Every other message -- whitespace, escapes, CR / LF inside base64, keys in
+ * another case or order, unknown keys, READY, a branch of another length,
+ * anything malformed -- gets status_out[i] = RBC_WIRE_FALLBACK and
+ * shard_lens_out[i] = 0; its other outputs are unspecified, and the caller
+ * runs it through the host decoder, which stays the authority on accepting
+ * it.  Nothing is written outside message i's own slots.
+ * All pointers are device memory, 16-byte aligned; row_pitch % 64 == 0. */
+#define RBC_HAS_WIRE_RX 1
+#define RBC_WIRE_OK 0
+#define RBC_WIRE_FALLBACK 1
+int rbc_dev_unmarshal_val(rbc_ctx *ctx, void *stream, int count, const uint8_t *msgs, const uint64_t *offs,
+                          const uint32_t *lens, const uint8_t *idx, uint8_t *rows, uint32_t row_pitch,
+                          uint32_t *shard_lens_out, uint8_t *branches_out, uint8_t *roots_out, uint8_t *types_out,
+                          int32_t *status_out);
+
+/* Validate ECHOs straight from their wire bytes; the shards stay on the
+ * device.  rbc_wire_rx owns a stream and the device buffers for up to
+ * max_msgs messages in a ring of up to max_ring_bytes per call, with one row
+ * slot of row_pitch bytes (row_pitch % 64 == 0, >= the largest shard) per
+ * message. */
+typedef struct rbc_wire_rx rbc_wire_rx;
+int rbc_wire_rx_create(rbc_ctx *ctx, int max_msgs, size_t max_ring_bytes, uint32_t row_pitch, rbc_wire_rx **out);
+void rbc_wire_rx_destroy(rbc_wire_rx *rx); /* waits for its outstanding work */
+/* One host-to-device copy of ring[0, ring_bytes) (direct DMA from
+ * rbc_host_alloc memory, staged from pageable memory), the unmarshal kernel
+ * into keep_dev (row i at keep_dev + i*row_pitch, keep_bytes >=
+ * count*row_pitch, device memory of the context's device), validateMessage of
+ * every decoded message against the root and branch it carries itself, and
+ * one device-to-host copy of the small outputs:
+ *   verdict_out[i]   1 valid, 0 decoded but the proof fails, 2 fallback (not
+ *                    canonical: no proof attempted, decode it on the host)
+ *   types_out[i], roots_out[i][32], shard_lens_out[i] (uint32), leaves_out[i][32]
+ *                    (the shard's SHA-256; nullable) -- defined for verdicts 0 and 1.
+ * leaves_out and the kept rows feed rbc_interpolate_batch_kept unchanged.
+ * Every argument is checked before any device work (offs[i] % 16 == 0,
+ * offs[i] + round_up(lens[i], 16) <= ring_bytes, idx[i] < n, count <=
+ * max_msgs, ring_bytes <= max_ring_bytes, keep_dev / keep_bytes as above):
+ * RBC_ERR_INVALID_ARG enqueues nothing.  Asynchronous: the outputs and the
+ * ring belong to the call until rbc_wire_wait(ticket) returns; a second
+ * rbc_wire_validate on the same rx first completes the one before. */
+int rbc_wire_validate(rbc_wire_rx *rx, int count, const uint8_t *ring, size_t ring_bytes, const uint64_t *offs,
+                      const uint32_t *lens, const uint8_t *idx, uint8_t *verdict_out, uint8_t *types_out,
+                      uint8_t *roots_out, uint32_t *shard_lens_out, uint8_t *leaves_out, uint8_t *keep_dev,
+                      size_t keep_bytes, uint64_t *ticket);
+int rbc_wire_wait(rbc_wire_rx *rx, uint64_t ticket);
+int rbc_wire_poll(rbc_wire_rx *rx, uint64_t ticket, int *done);
+
 /* ---- RBC instance (one proposer's broadcast, seen at one node) ----------- */
 typedef struct rbc_node rbc_node;
 /* NewRBC (rbc/rbc.go:38). */

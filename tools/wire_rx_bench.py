@@ -1,0 +1,268 @@
+#!/usr/bin/env python3
+"""One node's C2 epoch of received ECHOs, validated two ways in the same run.
+
+N = 128, f = 42; 1,024 instances x 86 ECHOs of S = 23,832-byte shards arrive as
+pb.Message bytes in a pinned ring (a pass-through gRPC codec's view).
+
+  A  the parent's path: rbc_pb_decode_rbc + rbc_json_decode_val on 16 host
+     threads into a pinned packed arena (tools/wire_rx_decode.cpp), then
+     rbc_validate_packed_keep.
+  B  rbc_wire_validate straight from the ring.
+  K  the unmarshal kernel alone on a device-resident ring, from events, beside
+     its byte floor (bytes read + written over the HBM rate DESIGN.md uses).
+
+Every leg is a child process of its own under its own time limit; the parent
+stops at the first one that fails.  Each leg runs --warmup (>= 2) epochs, then
+--epochs (>= 5) timed ones, and reports the median and the min-max spread.  The
+epoch is seeded, so the legs see the same bytes, and A's and B's verdicts must
+be identical (a digest of them is compared).  About 1 % of the messages carry
+one corrupted shard character, so both verdict values occur.
+
+  python tools/wire_rx_bench.py --out profiles/wire_rx/c2.json
+"""
+import argparse
+import ctypes
+import hashlib
+import json
+import os
+import statistics
+import subprocess
+import sys
+import threading
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+HBM_BPS = 8e12  # the roofline's HBM rate
+THREADS = 16
+
+
+def rup(x, a):
+    return (x + a - 1) // a * a
+
+
+def build_epoch(ca, ctx, a):
+    """The epoch's messages in a pinned ring: offs, lens, idx, and the commitment geometry."""
+    import numpy as np
+    n, k, d = ctx.n, ctx.k, ctx.depth
+    S = a.shard_len
+    rng = np.random.default_rng(a.seed)
+    distinct = min(a.distinct, a.instances)
+    values = [rng.integers(0, 256, k * S, dtype=np.uint8) for _ in range(distinct)]
+    c = ctx.shard_commit_batch(values)
+    pitch = rup(S, 64)
+    sh = np.zeros((distinct, n, pitch), np.uint8)
+    sh[:, :, :S] = c["shards"][:, :, :S]
+    out_pitch = rup(ctx.val_message_size(S, 0, 1), 16)
+    dsh, dbr, drt = ca.DeviceBuffer(sh.nbytes), ca.DeviceBuffer(distinct * n * d * 32), ca.DeviceBuffer(distinct * 32)
+    dout, dol = ca.DeviceBuffer(distinct * n * out_pitch), ca.DeviceBuffer(distinct * n * 4)
+    dsh.upload(sh)
+    dbr.upload(np.ascontiguousarray(c["branches"]).reshape(-1))
+    drt.upload(np.ascontiguousarray(c["roots"]).reshape(-1))
+    ctx.dev_marshal_val(None, distinct, 1, dsh, pitch, None, S, dbr, drt, dout, out_pitch, dol)
+    ca.rbc.lib.rbc_device_sync(0)
+    msgs = dout.download().reshape(distinct * n, out_pitch)
+    mlen = int(dol.download().view(np.uint32)[0])
+    for b in (dsh, dbr, drt, dout, dol):
+        b.free()
+    count = a.instances * a.echoes
+    slot = rup(mlen, 16)
+    ring = ca.pinned_empty(count * slot)
+    r2 = ring.reshape(count, slot)
+    idx = np.zeros(count, np.uint8)
+    for i in range(a.instances):
+        senders = np.sort(rng.permutation(n)[:a.echoes])
+        idx[i * a.echoes:(i + 1) * a.echoes] = senders
+        r2[i * a.echoes:(i + 1) * a.echoes] = msgs[(i % distinct) * n + senders, :slot]
+    # ~1 % corrupted: one shard character replaced by another of the alphabet
+    blk0 = mlen - 5 - (S + 2) // 3 * 4  # '"]}' + the ECHO type field behind the block
+    for m in rng.permutation(count)[:max(count // 100, 1)]:
+        at = blk0 + int(rng.integers(0, S // 3 * 4))
+        r2[m, at] = ord("A") if r2[m, at] != ord("A") else ord("B")
+    offs = np.arange(count, dtype=np.uint64) * slot
+    lens = np.full(count, mlen, np.uint32)
+    return {"ring": ring, "offs": offs, "lens": lens, "idx": idx, "count": count, "S": S, "mlen": mlen,
+            "wire_bytes": int(count) * mlen, "shard_bytes": int(count) * S}
+
+
+def timed(fn, warmup, epochs):
+    for _ in range(warmup):
+        fn()
+    ts = []
+    for _ in range(epochs):
+        t0 = time.perf_counter()
+        fn()
+        ts.append(time.perf_counter() - t0)
+    return ts
+
+
+def stats(ts, nbytes):
+    med = statistics.median(ts)
+    return {"median_s": med, "min_s": min(ts), "max_s": max(ts), "epochs_s": ts,
+            "median_GBps": nbytes / med / 1e9, "min_GBps": nbytes / max(ts) / 1e9, "max_GBps": nbytes / min(ts) / 1e9}
+
+
+def digest(v):
+    return hashlib.sha256(bytes(v)).hexdigest()
+
+
+def leg_a(ca, ctx, e, a):
+    import numpy as np
+    so = os.path.join(ROOT, "tools", "libwire_rx_decode.so")
+    if not os.path.exists(so):
+        subprocess.run(["make", "-C", os.path.join(ROOT, "tools"), "libwire_rx_decode.so"], check=True)
+    dec = ctypes.CDLL(so).wire_rx_decode_range
+    dec.restype = ctypes.c_int
+    dec.argtypes = [ctypes.c_void_p] * 3 + [ctypes.c_int] * 2 + [ctypes.c_void_p] * 2 + [ctypes.c_uint32,
+                   ctypes.c_void_p, ctypes.c_uint32] + [ctypes.c_void_p] * 3
+    count, S, d = e["count"], e["S"], ctx.depth
+    assert ctx.n % 2 == 0  # no empty level-0 sibling: the flat branch is the device form
+    pitch, bslot = rup(S, 64), max(d, 1) * 32
+    arena = ca.pinned_empty(count * pitch)
+    arena[:] = 0
+    aoffs = np.arange(count, dtype=np.uint64) * pitch
+    br, roots = ca.pinned_empty((count, bslot)), ca.pinned_empty((count, 32))
+    slens, types = np.zeros(count, np.uint32), np.zeros(count, np.uint8)
+    keep = ca.DeviceBuffer(arena.nbytes)
+    out = {"ok": ca.pinned_empty(count), "leaves": ca.pinned_empty((count, 32))}
+    bad = [0] * THREADS
+    edges = [count * t // THREADS for t in range(THREADS + 1)]
+    host_s = []
+
+    def work(t):
+        bad[t] = dec(e["ring"].ctypes.data, e["offs"].ctypes.data, e["lens"].ctypes.data, edges[t], edges[t + 1],
+                     arena.ctypes.data, aoffs.ctypes.data, pitch, br.ctypes.data, bslot, roots.ctypes.data,
+                     slens.ctypes.data, types.ctypes.data)
+
+    def epoch():
+        t0 = time.perf_counter()
+        th = [threading.Thread(target=work, args=(t,)) for t in range(THREADS)]
+        for x in th:
+            x.start()
+        for x in th:
+            x.join()
+        host_s.append(time.perf_counter() - t0)
+        assert sum(bad) == 0 and (slens == S).all()
+        ctx.validate_packed_submit(arena, aoffs, slens, e["idx"], br, roots, leaves=True, out=out, keep=keep).wait()
+
+    ts = timed(epoch, a.warmup, a.epochs)
+    verdict = (out["ok"][:count] != 0).astype(np.uint8)
+    r = stats(ts, e["shard_bytes"])
+    r.update(host_decode_median_s=statistics.median(host_s[a.warmup:]), verdict_sha256=digest(verdict),
+             valid=int(verdict.sum()), h2d_bytes=int(arena.nbytes))
+    return r
+
+
+def leg_b(ca, ctx, e, a):
+    count, S = e["count"], e["S"]
+    pitch = rup(S, 64)
+    rx = ca.WireRx(ctx, count, e["ring"].nbytes, pitch)
+    keep = ca.DeviceBuffer(count * pitch)
+    got = {}
+
+    def epoch():
+        got.update(rx.validate(e["ring"], e["offs"], e["lens"], e["idx"], keep))
+
+    ts = timed(epoch, a.warmup, a.epochs)
+    assert (got["verdict"] != 2).all(), "a message of the project's own encoder fell back"
+    r = stats(ts, e["shard_bytes"])
+    r.update(verdict_sha256=digest(got["verdict"]), valid=int((got["verdict"] == 1).sum()),
+             h2d_bytes=int(e["ring"].nbytes))
+    rx.close()
+    return r
+
+
+def leg_k(ca, ctx, e, a):
+    import numpy as np
+    count, S, d = e["count"], e["S"], ctx.depth
+    pitch, bslot = rup(S, 64), max(d, 1) * 32
+    dring = ca.DeviceBuffer(e["ring"].nbytes)
+    dring.upload(e["ring"])
+    doffs, dlens, didx = ca.DeviceBuffer(count * 8), ca.DeviceBuffer(count * 4), ca.DeviceBuffer(count)
+    doffs.upload(e["offs"])
+    dlens.upload(e["lens"])
+    didx.upload(e["idx"])
+    rows, slens, br = ca.DeviceBuffer(count * pitch), ca.DeviceBuffer(count * 4), ca.DeviceBuffer(count * bslot)
+    roots, types, status = ca.DeviceBuffer(count * 32), ca.DeviceBuffer(count), ca.DeviceBuffer(count * 4)
+    st = ca.Stream()
+    ms = []
+    for it in range(a.warmup + a.epochs):
+        e0, e1 = ca.Event(), ca.Event()
+        e0.record(st)
+        ctx.dev_unmarshal_val(st.ptr, count, dring, doffs, dlens, didx, rows, pitch, slens, br, roots, types, status)
+        e1.record(st)
+        st.sync()
+        if it >= a.warmup:
+            ms.append(e0.elapsed_ms(e1))
+    assert not status.download().view(np.int32).any()
+    read = count * (e["mlen"] + 13)                      # the message, offs, lens, idx
+    written = count * (pitch + (d * 32) + 32 + 4 + 1 + 4)  # row up to round_up(S, 64), branch, root, S, type, status
+    med = statistics.median(ms) / 1e3
+    floor = (read + written) / HBM_BPS
+    return {"median_s": med, "min_s": min(ms) / 1e3, "max_s": max(ms) / 1e3, "epochs_s": [m / 1e3 for m in ms],
+            "bytes_read": read, "bytes_written": written, "floor_s": floor, "floor_over_median": floor / med,
+            "achieved_TBps": (read + written) / med / 1e12}
+
+
+def child(a):
+    import cleisthenes_amd as ca
+    ctx = ca.Context(a.n, a.f)
+    e = build_epoch(ca, ctx, a)
+    r = {"A": leg_a, "B": leg_b, "K": leg_k}[a.leg](ca, ctx, e, a)
+    r.update(leg=a.leg, count=e["count"], shard_len=e["S"], message_len=e["mlen"], wire_bytes=e["wire_bytes"],
+             shard_bytes=e["shard_bytes"], library=os.path.relpath(ca.rbc.library_path(), ROOT))
+    print("WIRE_RX_LEG " + json.dumps(r), flush=True)
+
+
+def main():
+    p = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+    p.add_argument("--n", type=int, default=128)
+    p.add_argument("--f", type=int, default=42)
+    p.add_argument("--instances", type=int, default=1024)
+    p.add_argument("--echoes", type=int, default=86)
+    p.add_argument("--shard-len", type=int, default=23832)
+    p.add_argument("--distinct", type=int, default=16, help="distinct proposals behind the epoch's instances")
+    p.add_argument("--warmup", type=int, default=2)
+    p.add_argument("--epochs", type=int, default=5)
+    p.add_argument("--seed", type=int, default=20261019)
+    p.add_argument("--leg-timeout", type=int, default=240, help="seconds per leg")
+    p.add_argument("--out", default=None)
+    p.add_argument("--leg", choices=["A", "B", "K"], default=None, help=argparse.SUPPRESS)
+    a = p.parse_args()
+    if a.warmup < 2 or a.epochs < 5:
+        p.error("at least 2 warm-up and 5 timed epochs")
+    if a.leg:
+        return child(a)
+    legs = {}
+    for leg in ("A", "B", "K"):
+        cmd = [sys.executable, os.path.abspath(__file__), "--leg", leg] + \
+            [x for k in ("n", "f", "instances", "echoes", "shard_len", "distinct", "warmup", "epochs", "seed")
+             for x in ("--" + k.replace("_", "-"), str(getattr(a, k)))]
+        env = dict(os.environ, OMP_NUM_THREADS=os.environ.get("OMP_NUM_THREADS", str(THREADS)))
+        try:
+            r = subprocess.run(cmd, capture_output=True, text=True, timeout=a.leg_timeout, env=env)
+        except subprocess.TimeoutExpired:
+            sys.exit(f"leg {leg}: no result within {a.leg_timeout} s; stopping")
+        line = [x for x in r.stdout.splitlines() if x.startswith("WIRE_RX_LEG ")]
+        if r.returncode != 0 or not line:
+            sys.stderr.write(r.stdout[-2000:] + r.stderr[-4000:])
+            sys.exit(f"leg {leg} failed (exit {r.returncode}); stopping")
+        legs[leg] = json.loads(line[-1][len("WIRE_RX_LEG "):])
+    same = legs["A"]["verdict_sha256"] == legs["B"]["verdict_sha256"]
+    res = {"bench": "wire_rx", "geometry": {"n": a.n, "f": a.f, "instances": a.instances, "echoes": a.echoes,
+                                            "shard_len": a.shard_len}, "threads": THREADS, "warmup": a.warmup,
+           "epochs": a.epochs, "verdicts_identical": same, "A_parent_decode_then_validate_packed_keep": legs["A"],
+           "B_wire_validate": legs["B"], "K_unmarshal_kernel": legs["K"],
+           "B_over_A_median": legs["A"]["median_s"] / legs["B"]["median_s"]}
+    text = json.dumps(res, indent=1)
+    if a.out:
+        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+        with open(a.out, "w") as fh:
+            fh.write(text + "\n")
+    print(text)
+    if not same:
+        sys.exit("the two legs' verdicts differ")
+
+
+if __name__ == "__main__":
+    main()
