@@ -32,9 +32,6 @@ namespace {
 constexpr size_t kAlign = 64;
 inline size_t round_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
 
-// Rows per GF chunk (accumulators held in VGPRs) of the matrix codec.
-constexpr int kGfRcMax = 21;
-
 int tree_width(int n) {
     int w = 1;
     while (w < n) w <<= 1;

@@ -23,6 +23,38 @@ inline bool rbc_fft_supported(int n, int k) {
     return false;
 }
 
+// Trees (merkle_kernel) or instances (merkle_recheck_kernel) packed into each
+// one-wave block of `count` trees of `width` leaves: up to 512 / W (<= 64, 16 KiB
+// of node LDS), halved until the grid has >= 512 blocks so that a small batch
+// still spreads over every CU (C2 and C4: 2 trees per block).
+// (C4, W = 256, measured: 1 tree per block 0.68 ms, 2 trees 0.63, 4 trees 0.95;
+// in the pipelined step 4 trees per block equal to 2 at C2 and C4, gpu_r04l.sh)
+inline int rbc_trees_per_block(int width, int count) {
+    int g = width >= 512 ? 1 : (512 / width < 64 ? 512 / width : 64);
+    while (g > 1 && (count + g - 1) / g < 512) g >>= 1;
+    return g;
+}
+
+// Rows per GF chunk (accumulators held in VGPRs) of the matrix codec.
+constexpr int kGfRcMax = 21;
+// The RC values gf_rows_kernel is instantiated for (rbc_launch_gf_rows).
+constexpr int kRC[] = {1,  2,  3,  4,  5,  6,  7,  8,  9,  10, 11, 12, 13, 14, 15, 16, 17,
+                       18, 19, 20, 21, 22, 23, 24, 26, 28, 30, 32, 36, 40, 42, 44, 48};
+
+// The body of rbc_gf_pick_rc (kernels.h; defined beside the launchers in
+// kernels.hip, so a host-only build may link a stand-in for it).
+inline int rbc_gf_pick_rc_impl(int R, int rcmax) {
+    // fewest chunks of <= rcmax rows, then the smallest instantiated RC covering them
+    if (R <= 0) return 1;
+    if (rcmax < 1) rcmax = 1;
+    if (rcmax > 48) rcmax = 48;
+    const int chunks = (R + rcmax - 1) / rcmax;
+    const int want = (R + chunks - 1) / chunks;
+    for (int rc : kRC)
+        if (rc >= want) return rc;
+    return 48;
+}
+
 // klauspost Split's data shards without copying whole rows (rbc/rbc.go:97-100:
 // Split returns slices of the caller's value, and allocates only where it has
 // to pad).  With S = ceil(len / k), row j is data[j*S, (j+1)*S) itself while it

@@ -254,7 +254,7 @@ hipError_t rbc_launch_unmarshal_val(const WireRxArgs &a, hipStream_t st);
 
 hipError_t rbc_launch_rs_fft(const FftArgs &a, hipStream_t st);
 
-int rbc_gf_pick_rc(int R, int rcmax);
+int rbc_gf_pick_rc(int R, int rcmax);  // GfArgs::rc; the rule is host_shared.h's rbc_gf_pick_rc_impl
 hipError_t rbc_launch_gf_rows(const GfArgs &a, hipStream_t st);
 // interpolate's missing data rows (FFT codec, gf_regen.hip): one wave per column tile of 256 * W
 // bytes owns every row (W and the tiles chosen from the row length); needs rcount (row count <= R)

@@ -1957,21 +1957,9 @@ static hipError_t launch_gf_rc(const GfArgs &a, hipStream_t st) {
     return hipGetLastError();
 }
 
-static const int kRC[] = {1,  2,  3,  4,  5,  6,  7,  8,  9,  10, 11, 12, 13, 14, 15, 16, 17,
-                          18, 19, 20, 21, 22, 23, 24, 26, 28, 30, 32, 36, 40, 42, 44, 48};
+int rbc_gf_pick_rc(int R, int rcmax) { return rbc_gf_pick_rc_impl(R, rcmax); }
 
-int rbc_gf_pick_rc(int R, int rcmax) {
-    // fewest chunks of <= rcmax rows, then the smallest instantiated RC covering them
-    if (R <= 0) return 1;
-    if (rcmax < 1) rcmax = 1;
-    if (rcmax > 48) rcmax = 48;
-    const int chunks = (R + rcmax - 1) / rcmax;
-    const int want = (R + chunks - 1) / chunks;
-    for (int rc : kRC)
-        if (rc >= want) return rc;
-    return 48;
-}
-
+// a.rc comes from rbc_gf_pick_rc: one case per kRC entry (host_shared.h)
 hipError_t rbc_launch_gf_rows(const GfArgs &a, hipStream_t st) {
     if (a.count <= 0 || (a.R <= 0 && !a.copy)) return hipSuccess;
     if (a.tpb != 0 && a.tpb != 256) return hipErrorInvalidValue;
@@ -2073,13 +2061,7 @@ hipError_t rbc_launch_merkle(const MerkleArgs &a, bool check, hipStream_t st) {
     if (a.width < 1 || a.width > 1024 || (a.width & (a.width - 1)) || (1 << a.depth) != a.width)
         return hipErrorInvalidValue;
     MerkleArgs b = a;
-    // up to 512 / W trees per block (<= 64), but keep >= 512 blocks so that a
-    // small batch still spreads over every CU (C2 and C4: 2 trees per block)
-    // (C4, W = 256, measured: 1 tree per block 0.68 ms, 2 trees 0.63, 4 trees 0.95;
-    // in the pipelined step 4 trees per block equal to 2 at C2 and C4, gpu_r04l.sh)
-    int g = a.width >= 512 ? 1 : (512 / a.width < 64 ? 512 / a.width : 64);
-    while (g > 1 && (a.count + g - 1) / g < 512) g >>= 1;
-    b.trees_per_block = g;
+    b.trees_per_block = rbc_trees_per_block(a.width, a.count);
     // W = 256 builds with branches: the top five layers in merkle_top_kernel
     // (C4: build VALU 265 -> 158 + 35 M, the step 370.9-371.0 -> 376.7-378.6 GB/s, gpu_r04t.sh)
     b.stop_m = (!check && a.width == 256 && a.depth == 8 && a.branches && a.n > 128) ? 32 : 0;
@@ -2100,10 +2082,8 @@ hipError_t rbc_launch_recheck(const RecheckArgs &a, hipStream_t st) {
     if (a.width < 2 || a.width > 256 || (a.width & (a.width - 1)) || (1 << a.depth) != a.width)
         return hipErrorInvalidValue;
     RecheckArgs b = a;
-    // G instances per one-wave block: 512 / W leaves' worth (16 KiB of node
-    // LDS), but >= 512 blocks so that a small batch still spreads over the CUs
-    int g = std::min(512 / a.width, 64);
-    while (g > 1 && (a.count + g - 1) / g < 512) g >>= 1;
+    // G instances per one-wave block, by the rule of the build's trees
+    const int g = rbc_trees_per_block(a.width, a.count);
     b.inst_per_block = g;
     const size_t lds = (size_t)g * a.width * 32 + (size_t)g * 2 * a.width + (size_t)g * a.width;
     const unsigned blocks = (unsigned)((a.count + g - 1) / g);

@@ -1305,10 +1305,11 @@ def test_device_verify_ragged_lengths(gpu, ref, n, f):
         assert 1 <= (got[i] == 0).sum() <= 2
 
 
-# every tree depth 1..8 (W = 2..256), non-power-of-two N, and an odd instance
-# count so the last merkle block holds fewer trees than trees_per_block: the
-# branch-write loop steps (j, l) by (32 / d, 32 % d) with a carry, so each
-# depth exercises a different stepping
+# every tree depth 1..8 (W = 2..256) and non-power-of-two N: the branch-write
+# loop steps (j, l) by (32 / d, 32 % d) with a carry, so each depth exercises a
+# different stepping.  Five instances run one tree per block (the launcher packs
+# trees only from 1024 instances on); the packed blocks, a partly filled last
+# one included, are in tests/test_gpu_packed_merkle.py
 @pytest.mark.gpu
 @pytest.mark.parametrize("n,f", [(2, 0), (3, 1), (6, 1), (11, 3), (17, 5), (32, 10), (33, 10), (100, 33),
                                  (129, 42), (256, 85)])
