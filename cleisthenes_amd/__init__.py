@@ -15,11 +15,12 @@ from .rbc import (  # noqa: F401
     RBCError,
     Stream,
     Event,
+    WireReceiver,
     WireRx,
     device_count,
     pinned_empty,
     split_rows,
 )
 
-__all__ = ["Batcher", "Context", "DeviceBuffer", "Encoder", "RBCError", "Stream", "Event", "WireRx", "device_count",
-           "pinned_empty", "split_rows"]
+__all__ = ["Batcher", "Context", "DeviceBuffer", "Encoder", "RBCError", "Stream", "Event", "WireReceiver", "WireRx",
+           "device_count", "pinned_empty", "split_rows"]

@@ -189,6 +189,17 @@ _SIGS = {
                                   c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, POINTER(c_uint64)]),
     "rbc_wire_wait": (c_int, [c_void_p, c_uint64]),
     "rbc_wire_poll": (c_int, [c_void_p, c_uint64, POINTER(c_int)]),
+    # ECHOs from wire bytes to delivered values (RBC_HAS_WIRE_RECEIVE)
+    "rbc_dev_unmarshal_echo": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p,
+                                       c_void_p, c_void_p, c_void_p, c_uint32, c_void_p, c_uint32, c_void_p, c_void_p,
+                                       c_void_p, c_void_p]),
+    "rbc_wire_receiver_create": (c_int, [c_void_p, c_int, c_int, c_size_t, c_uint32, POINTER(c_void_p)]),
+    "rbc_wire_receiver_destroy": (None, [c_void_p]),
+    "rbc_wire_receive": (c_int, [c_void_p, c_int, c_int, c_void_p, c_size_t, c_void_p, c_void_p, c_void_p, c_void_p,
+                                 c_void_p, szp, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p, i32p,
+                                 POINTER(c_uint64)]),
+    "rbc_wire_receive_wait": (c_int, [c_void_p, c_uint64]),
+    "rbc_wire_receive_poll": (c_int, [c_void_p, c_uint64, POINTER(c_int)]),
     # parity-only shard commit (RBC_HAS_SHARD_COMMIT_PARITY)
     "rbc_dev_shard_commit_parity": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_uint64, c_void_p, c_uint32,
                                             c_void_p, c_void_p, c_uint32, c_void_p, c_void_p, c_void_p, c_void_p]),
@@ -208,14 +219,18 @@ _SIGS = {
 }
 
 # Additions made at an unchanged ABI version are detected by symbol, as their
-# header macros say (RBC_HAS_WIRE_RX): another build of ABI 7 (RBC_GPU_LIB)
-# may lack them.  They are then left unbound, and using one raises.
+# header macros say (RBC_HAS_WIRE_RX, RBC_HAS_WIRE_RECEIVE): another build of
+# ABI 7 (RBC_GPU_LIB) may lack them.  They are then left unbound, and using one
+# raises.
 _BY_SYMBOL = ("rbc_dev_unmarshal_val", "rbc_wire_rx_create", "rbc_wire_rx_destroy", "rbc_wire_validate",
               "rbc_wire_wait", "rbc_wire_poll")
+_BY_SYMBOL_RECEIVE = ("rbc_dev_unmarshal_echo", "rbc_wire_receiver_create", "rbc_wire_receiver_destroy",
+                      "rbc_wire_receive", "rbc_wire_receive_wait", "rbc_wire_receive_poll")
 HAS_WIRE_RX = all(hasattr(lib, _name) for _name in _BY_SYMBOL)
+HAS_WIRE_RECEIVE = all(hasattr(lib, _name) for _name in _BY_SYMBOL_RECEIVE)
 
 for _name, (_res, _args) in _SIGS.items():
-    if _name in _BY_SYMBOL and not HAS_WIRE_RX:
+    if (_name in _BY_SYMBOL and not HAS_WIRE_RX) or (_name in _BY_SYMBOL_RECEIVE and not HAS_WIRE_RECEIVE):
         continue
     _fn = getattr(lib, _name)
     _fn.restype = _res
@@ -225,6 +240,11 @@ for _name, (_res, _args) in _SIGS.items():
 def require_wire_rx() -> None:
     if not HAS_WIRE_RX:
         raise ImportError(f"{LIB_PATH} has no wire receive path (RBC_HAS_WIRE_RX): rbc_dev_unmarshal_val missing")
+
+
+def require_wire_receive() -> None:
+    if not HAS_WIRE_RECEIVE:
+        raise ImportError(f"{LIB_PATH} has no wire receiver (RBC_HAS_WIRE_RECEIVE): rbc_wire_receive missing")
 
 
 def header_functions(path: str = None):
@@ -261,6 +281,8 @@ RBC_ERR_PROTOCOL = -20  # include/rbc_protocol.h
 RBC_MSG_VAL, RBC_MSG_ECHO, RBC_MSG_READY = 0, 1, 2
 # rbc_dev_unmarshal_val status (include/rbc_protocol.h)
 RBC_WIRE_OK, RBC_WIRE_FALLBACK = 0, 1
+# rbc_dev_unmarshal_echo adds (RBC_HAS_WIRE_RECEIVE)
+RBC_WIRE_OTHER_ROOT, RBC_WIRE_OTHER_LEN = 2, 3
 
 
 class RBCError(Exception):

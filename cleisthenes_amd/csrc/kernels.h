@@ -228,7 +228,7 @@ struct WireArgs {
 hipError_t rbc_launch_marshal_val(const WireArgs &a, hipStream_t st);
 
 // Per-message status of the unmarshal kernel (include/rbc_protocol.h)
-enum { WIRE_OK = 0, WIRE_FALLBACK = 1 };
+enum { WIRE_OK = 0, WIRE_FALLBACK = 1, WIRE_OTHER_ROOT = 2, WIRE_OTHER_LEN = 3 };
 
 // VAL / ECHO unmarshaling (wire.hip), the inverse: message i is the bytes
 // msgs[offs[i], offs[i] + lens[i]) from the node at Merkle leaf idx[i].  A
@@ -251,6 +251,36 @@ struct WireRxArgs {
     int32_t *status;       // [count] WIRE_OK / WIRE_FALLBACK
 };
 hipError_t rbc_launch_unmarshal_val(const WireRxArgs &a, hipStream_t st);
+
+// ECHO unmarshaling into the receiver's batch layout (wire.hip,
+// unmarshal_echo_kernel): message m, read like WireRxArgs' message i, belongs
+// to instance inst[m] and goes to slot r = inst[m]*n + idx[m] of shards /
+// branches / present -- the rbc_rx_batch layout, so every shard is written
+// once, where verify and decode read it.  Status in this order: shape not
+// derivable (WireRxArgs' rule, inst[m] >= count included) -> WIRE_FALLBACK;
+// derived S != the instance's length -> WIRE_OTHER_LEN, nothing of the slot
+// written; a byte not canonical -> WIRE_FALLBACK; the message's root (decoded
+// in registers, never stored) != roots[inst[m]] -> WIRE_OTHER_ROOT; else
+// WIRE_OK and present[r] = 1.  Nothing is written outside message m's own
+// slots; two messages naming one slot are the caller's error.
+struct WireEchoArgs {
+    int count, msgs, n, depth;   // instances, messages
+    const uint8_t *ring;
+    const uint64_t *offs;        // [msgs] % 16 == 0
+    const uint32_t *lens;        // [msgs]
+    const uint32_t *inst;        // [msgs] < count
+    const uint8_t *idx;          // [msgs] sender's leaf index
+    const uint8_t *roots;        // [count][32] the root each instance collects ECHOs for
+    const uint32_t *shard_lens;  // [count], or NULL: uniform_len
+    uint32_t uniform_len;
+    uint8_t *shards;             // [count][n][shard_pitch], zeros from S to round_up(S, 64)
+    uint32_t shard_pitch;        // % 64 == 0
+    uint8_t *branches;           // [count][n][max(depth,1)][32], device form
+    uint8_t *present;            // [count][n]: 1 written for WIRE_OK, else untouched
+    int32_t *msg_status;         // [msgs]
+    uint8_t *types;              // [msgs], nullable
+};
+hipError_t rbc_launch_unmarshal_echo(const WireEchoArgs &a, hipStream_t st);
 
 hipError_t rbc_launch_rs_fft(const FftArgs &a, hipStream_t st);
 

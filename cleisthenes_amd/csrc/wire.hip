@@ -20,7 +20,9 @@
 //
 // The receive side (unmarshal_val_kernel, below the marshal kernel) is the
 // inverse: canonical messages decoded back into the device forms, everything
-// else left to the host decoder.
+// else left to the host decoder.  unmarshal_echo_kernel is the same decode
+// for a receiver that batches an epoch's ECHOs: it writes each shard and
+// branch once, at the leaf position of its instance's shard set.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -424,7 +426,115 @@ __global__ __launch_bounds__(256) void unmarshal_val_kernel(WireRxArgs a) {
     }
 }
 
+// unmarshal_echo_kernel: unmarshal_val_kernel for a receiver that already
+// knows which instance a message belongs to and which root that instance
+// collects ECHOs for.  The shard and the branch go straight to slot
+// r = inst*n + idx of the rbc_rx_batch layout (what sha_rows / the decode
+// read), so a shard is written once; the message's root is only compared, in
+// registers, with roots[inst].  Same shape derivation, same byte checks, same
+// chunk decode; the status order is kernels.h's (WireEchoArgs).
+// one wave per message; 4 waves (messages) per block
+__global__ __launch_bounds__(256) void unmarshal_echo_kernel(WireEchoArgs a) {
+    const uint32_t i = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (i >= (uint32_t)a.msgs) return;
+    const uint32_t lane = threadIdx.x & 63;
+    const uint32_t total = a.lens[i], j = a.idx[i], in = a.inst[i];
+    const uint8_t *m = a.ring + a.offs[i];
+    const bool empty0 = a.depth > 0 && (int)(j ^ 1u) >= a.n;
+    const uint32_t br_len = 32u * (a.depth - (empty0 ? 1 : 0));
+    // the shape, from the length and the leaf alone (wave-uniform)
+    Layout L;
+    int type = 0;
+    bool shaped = j < (uint32_t)a.n && in < (uint32_t)a.count && rx_layout(total, br_len, L, type);
+    uint32_t S = 0;
+    if (shaped) {
+        const uint32_t pad = m[L.end_lit_off - 1] == '=' ? (m[L.end_lit_off - 2] == '=' ? 2u : 1u) : 0u;
+        S = L.S - pad;
+        shaped = S <= a.shard_pitch;
+    }
+    if (!shaped) {
+        if (lane == 0) {
+            a.msg_status[i] = WIRE_FALLBACK;
+            if (a.types) a.types[i] = 0;
+        }
+        return;
+    }
+    // a shard of another length than its instance's: the slot stays as it is
+    if (S != (a.shard_lens ? a.shard_lens[in] : a.uniform_len)) {
+        if (lane == 0) {
+            a.msg_status[i] = WIRE_OTHER_LEN;
+            if (a.types) a.types[i] = (uint8_t)type;
+        }
+        return;
+    }
+    L.S = S;
+    uint32_t bad = 0, other = 0;
+    // header, JSON literals and type field: at most 12 + 13 + 26 + 3 + 2 bytes, one per lane
+    {
+        const uint32_t head = L.hdr + 13, mid = br_len ? 24u : 26u;
+        const uint32_t nn = head + mid + 3 + (type ? 2u : 0u);
+        if (lane < nn) {
+            uint32_t p;
+            if (lane < head) {
+                p = lane;
+            } else {
+                const uint32_t k = lane - head;
+                if (k >= mid) p = L.end_lit_off + (k - mid);  // '"]}' and the type field behind it
+                else if (br_len && k >= 12) p = L.blk_lit_off + (k - 12);
+                else p = L.br_lit_off + k;
+            }
+            if (m[p] != msg_byte(L, p, type, nullptr, nullptr, nullptr)) bad = 1;
+        }
+    }
+    // the three base64 runs, one 16-byte chunk of decoded bytes per lane-step;
+    // the two chunks of the root are compared, not stored
+    const uint32_t nblk = ((S + 63u) & ~63u) >> 4, nbr = br_len >> 4, nq = nblk + nbr + 2;
+    const size_t r = (size_t)in * a.n + j;
+    uint8_t *row = a.shards + r * a.shard_pitch;
+    uint8_t *slot = a.branches + r * (a.depth > 1 ? a.depth : 1) * 32u;
+    const uint8_t *want_root = a.roots + (size_t)in * 32;
+    for (uint32_t q = lane; q < nq; q += 64) {
+        uint32_t off, len, o0;
+        uint8_t *dst;
+        if (q < nblk) {
+            off = L.blk_off, len = S, o0 = q << 4;
+            dst = row;
+        } else if (q < nblk + nbr) {
+            off = L.br_off, len = br_len, o0 = (q - nblk) << 4;
+            dst = slot + (empty0 ? 32u : 0u);
+        } else {
+            off = L.root_off, len = 32, o0 = (q - nblk - nbr) << 4;
+            dst = nullptr;
+        }
+        uint4 v = make_uint4(0, 0, 0, 0);
+        if (o0 < len) {
+            if (4 * (o0 / 3) + 24 <= len / 3 * 4) v = unb64_chunk16(m, off, o0, bad);
+            else v = unb64_chunk_slow(m, off, len, o0, bad);
+        }
+        if (dst) {
+            *reinterpret_cast<uint4 *>(dst + o0) = v;
+        } else {
+            const uint4 w = *reinterpret_cast<const uint4 *>(want_root + o0);
+            other |= (v.x ^ w.x) | (v.y ^ w.y) | (v.z ^ w.z) | (v.w ^ w.w);
+        }
+    }
+    // the zero slot of an empty level-0 sibling (or of a depth-0 tree)
+    if ((empty0 || a.depth == 0) && lane < 2) reinterpret_cast<uint4 *>(slot)[lane] = make_uint4(0, 0, 0, 0);
+    const bool fail = __any(bad != 0), wrong = __any(other != 0);
+    if (lane == 0) {
+        a.msg_status[i] = fail ? WIRE_FALLBACK : wrong ? WIRE_OTHER_ROOT : WIRE_OK;
+        if (a.types) a.types[i] = (uint8_t)type;
+        if (!fail && !wrong) a.present[r] = 1;
+    }
+}
+
 }  // namespace
+
+hipError_t rbc_launch_unmarshal_echo(const WireEchoArgs &a, hipStream_t st) {
+    if (a.msgs <= 0) return hipSuccess;
+    hipLaunchKernelGGL(unmarshal_echo_kernel, dim3(((unsigned)a.msgs + 3) / 4), dim3(256), 0, st, a);
+    return hipGetLastError();
+}
 
 hipError_t rbc_launch_unmarshal_val(const WireRxArgs &a, hipStream_t st) {
     if (a.count <= 0) return hipSuccess;

@@ -735,6 +735,17 @@ class Context:
                                         _dv(rows), row_pitch, _dv(shard_lens_out), _dv(branches_out), _dv(roots_out),
                                         _dv(types_out), _dv(status_out)), "rbc_dev_unmarshal_val")
 
+    def dev_unmarshal_echo(self, stream, count, msgs, ring, offs, lens, inst, idx, roots, shard_lens, uniform_len,
+                           shards, shard_pitch, branches, present, msg_status, types=None):
+        """Received ECHO pb.Message bytes decoded straight into the [count][n]
+        receiver layout (include/rbc_protocol.h): msg_status 0 = decoded, 1 = not
+        canonical, 2 = another root than its instance's, 3 = another length."""
+        _lib.require_wire_receive()
+        check(lib.rbc_dev_unmarshal_echo(self._p, _dv(stream), count, msgs, _dv(ring), _dv(offs), _dv(lens), _dv(inst),
+                                         _dv(idx), _dv(roots), _dv(shard_lens), uniform_len, _dv(shards), shard_pitch,
+                                         _dv(branches), _dv(present), _dv(msg_status), _dv(types)),
+              "rbc_dev_unmarshal_echo")
+
     def val_message_size(self, shard_len: int, index: int = 0, msg_type: int = 0) -> int:
         return lib.rbc_val_message_size(self.n, shard_len, index, msg_type)
 
@@ -836,6 +847,82 @@ class WireRx:
                     self_._keep = None
                 return {k: v[:count] for k, v in out.items()}
         return _W(self.ctx, t.value, None, keep=(ring, o, ln, ix, out, keep))
+
+
+class WireReceiver:
+    """rbc_wire_receiver (include/rbc_protocol.h): a ring of received ECHO
+    messages in, every instance's value, digest and status out, in one
+    submission.  While one is in flight the context must not run dev_verify,
+    dev_interpolate or dev_receive_step work on another stream."""
+
+    def __init__(self, ctx: Context, max_count: int, max_msgs: int, max_ring_bytes: int, shard_pitch: int):
+        _lib.require_wire_receive()
+        p = c_void_p()
+        check(lib.rbc_wire_receiver_create(ctx._p, max_count, max_msgs, max_ring_bytes, shard_pitch, byref(p)),
+              "rbc_wire_receiver_create")
+        self._p, self.ctx, self.shard_pitch = p, ctx, shard_pitch
+
+    def close(self) -> None:
+        if getattr(self, "_p", None):
+            lib.rbc_wire_receiver_destroy(self._p)
+            self._p = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def receive(self, ring: np.ndarray, offs, lens, inst, idx, roots, shard_lens, **kw) -> dict:
+        return self.receive_submit(ring, offs, lens, inst, idx, roots, shard_lens, **kw).wait()
+
+    def receive_submit(self, ring: np.ndarray, offs, lens, inst, idx, roots: np.ndarray, shard_lens,
+                       ring_bytes: Optional[int] = None, values_out: Optional[np.ndarray] = None) -> "HostTicket":
+        """Asynchronous rbc_wire_receive: message m is ring[offs[m] : offs[m] +
+        lens[m]] (offs[m] % 16 == 0), sent by the member at leaf idx[m] for
+        instance inst[m], which collects ECHOs for roots[inst[m]] and has shards
+        of shard_lens[inst[m]] bytes.  .wait() returns verdict [msgs] (1 proven,
+        0 the proof fails or another root, 2 fallback to the host decoder,
+        3 another length), types [msgs], valid [count][n], values
+        [count][value_pitch], digests [count][32] and status [count]; values_out
+        (e.g. pinned_empty((count, k*S_max))) receives the values in place."""
+        msgs, count = len(offs), len(shard_lens)
+        assert isinstance(ring, np.ndarray) and ring.dtype == np.uint8 and ring.flags.c_contiguous
+        o = np.ascontiguousarray(offs, dtype=np.uint64)
+        ln = np.ascontiguousarray(lens, dtype=np.uint32)
+        it = np.ascontiguousarray(inst, dtype=np.uint32)
+        ix = np.ascontiguousarray(idx, dtype=np.uint8)
+        rt = np.ascontiguousarray(roots, dtype=np.uint8)
+        assert len(ln) == msgs and len(it) == msgs and len(ix) == msgs and rt.size == count * 32
+        sl = (c_size_t * max(count, 1))(*[int(x) for x in shard_lens])
+        n, m, c = self.ctx.n, max(msgs, 1), max(count, 1)
+        vp = self.ctx.k * max([int(x) for x in shard_lens], default=1)
+        out = {"verdict": np.zeros(m, np.uint8), "types": np.zeros(m, np.uint8), "valid": np.zeros((c, n), np.uint8),
+               "values": values_out if values_out is not None else np.zeros((c, max(vp, 1)), np.uint8),
+               "digests": np.zeros((c, 32), np.uint8), "status": np.zeros(c, np.int32)}
+        values = out["values"]
+        assert values.dtype == np.uint8 and values.ndim == 2 and values.shape[0] >= count
+        t = c_uint64(0)
+        check(lib.rbc_wire_receive(self._p, count, msgs, _ptr(ring), ring.nbytes if ring_bytes is None else ring_bytes,
+                                   _ptr(o), _ptr(ln), _ptr(it), _ptr(ix), _ptr(rt), sl, _ptr(out["verdict"]),
+                                   _ptr(out["types"]), _ptr(out["valid"]), _ptr(values), values.strides[0],
+                                   _ptr(out["digests"]), out["status"].ctypes.data_as(_lib.i32p), byref(t)),
+              "rbc_wire_receive")
+        rcv = self
+        per_msg = ("verdict", "types")
+
+        class _R(HostTicket):
+            def done(self_) -> bool:
+                d = c_int(0)
+                check(lib.rbc_wire_receive_poll(rcv._p, self_.ticket, byref(d)), "rbc_wire_receive_poll")
+                return bool(d.value)
+
+            def wait(self_) -> dict:
+                if self_._keep is not None:
+                    check(lib.rbc_wire_receive_wait(rcv._p, self_.ticket), "rbc_wire_receive_wait")
+                    self_._keep = None
+                return {k: v[:msgs] if k in per_msg else v[:count] for k, v in out.items()}
+        return _R(self.ctx, t.value, None, keep=(ring, o, ln, it, ix, rt, sl, out))
 
 
 class Encoder:

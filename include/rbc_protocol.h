@@ -159,6 +159,96 @@ int rbc_wire_validate(rbc_wire_rx *rx, int count, const uint8_t *ring, size_t ri
 int rbc_wire_wait(rbc_wire_rx *rx, uint64_t ticket);
 int rbc_wire_poll(rbc_wire_rx *rx, uint64_t ticket, int *done);
 
+/* ---- ECHOs from wire bytes to delivered values in one call ----------------
+ * The mirror of rbc_shard_commit_val, present when RBC_HAS_WIRE_RECEIVE is
+ * defined (the ABI version stays 7: detect the addition by symbol).
+ *
+ * rbc_dev_unmarshal_echo decodes `msgs` received ECHO / VAL messages of
+ * `count` instances straight into the rbc_rx_batch layout, so its outputs feed
+ * rbc_dev_verify, rbc_dev_interpolate or rbc_dev_receive_step unchanged and
+ * every shard is written once, at its leaf position.  Message m is
+ * ring[offs[m], offs[m] + lens[m]) with the rules of rbc_dev_unmarshal_val
+ * (offs[m] % 16 == 0, no byte read outside round_up(lens[m], 16) from
+ * offs[m]); it was sent by the member at leaf idx[m] for instance
+ * inst[m] < count, which collects ECHOs for roots[inst[m]] and whose shards
+ * have shard_lens[inst[m]] bytes (shard_lens NULL: uniform_shard_len).  Its
+ * slot is r = inst[m]*n + idx[m] of shards [count][n][shard_pitch], branches
+ * [count][n][max(depth,1)][32] (device form: a zero slot for an empty level-0
+ * sibling) and present [count][n].  msg_status[m], decided in this order:
+ *   1. the shape cannot be derived from lens[m] and idx[m] (rbc_dev_unmarshal_val's
+ *      rule)                                          -> RBC_WIRE_FALLBACK
+ *   2. the derived shard length is not the instance's -> RBC_WIRE_OTHER_LEN;
+ *      nothing of the slot is written
+ *   3. a byte is not canonical                        -> RBC_WIRE_FALLBACK
+ *   4. the message's root (compared on the device, never stored) is not
+ *      roots[inst[m]]                                 -> RBC_WIRE_OTHER_ROOT
+ *   5. otherwise RBC_WIRE_OK: present[r] = 1, the row holds the shard with
+ *      zeros from S to round_up(S, 64), the branch slot the device-form branch.
+ * For statuses 1 and 2 present[r] is not written and the slot's row and branch
+ * bytes are unspecified.  types[m] (types nullable) is the message's type for
+ * RBC_WIRE_OK.  A message writes nothing outside its own row slot, branch
+ * slot, present[r], msg_status[m] and types[m]; two messages naming one slot
+ * are the caller's error.  All pointers are device memory, 16-byte aligned;
+ * shard_pitch % 64 == 0 and >= every shard_lens[i].  The caller zeroes present
+ * before the call, and shards where its consumer needs whole-pitch zeros. */
+#define RBC_HAS_WIRE_RECEIVE 1
+#define RBC_WIRE_OTHER_ROOT 2
+#define RBC_WIRE_OTHER_LEN 3
+int rbc_dev_unmarshal_echo(rbc_ctx *ctx, void *stream, int count, int msgs, const uint8_t *ring,
+                           const uint64_t *offs, const uint32_t *lens, const uint32_t *inst, const uint8_t *idx,
+                           const uint8_t *roots, const uint32_t *shard_lens, uint32_t uniform_shard_len,
+                           uint8_t *shards, uint32_t shard_pitch, uint8_t *branches, uint8_t *present,
+                           int32_t *msg_status, uint8_t *types);
+
+/* The receiver: a ring of received ECHO pb.Messages for `count` instances
+ * goes in; each instance's value, digest and status come out, from one
+ * submission.  rbc_wire_receiver owns one stream and the device buffers
+ * (shards, branches, present, valid, leaves, values, digests, status,
+ * metadata) for up to max_count instances and max_msgs messages in a ring of
+ * up to max_ring_bytes per call, with rows of shard_pitch bytes
+ * (shard_pitch % 64 == 0, >= the largest shard). */
+typedef struct rbc_wire_receiver rbc_wire_receiver;
+int rbc_wire_receiver_create(rbc_ctx *ctx, int max_count, int max_msgs, size_t max_ring_bytes, uint32_t shard_pitch,
+                             rbc_wire_receiver **out);
+void rbc_wire_receiver_destroy(rbc_wire_receiver *rcv); /* waits for its outstanding work */
+/* On the receiver's own stream: one host-to-device copy of the metadata, one
+ * of ring[0, ring_bytes) (direct DMA from rbc_host_alloc memory, staged from
+ * pageable memory), rbc_dev_unmarshal_echo into zeroed rows, rbc_dev_verify
+ * over the decoded rows, rbc_dev_interpolate(leaves_verified = 1) over the
+ * proven ones, and the copies back:
+ *   verdict_out[m]  1 decoded and proven; 0 decoded, but the proof fails or
+ *                   the root is another one; 2 fallback (not canonical: decode
+ *                   it on the host); 3 the shard has another length than its
+ *                   instance
+ *   types_out[m]    (nullable) the message's type, for verdicts 0 and 1
+ *   valid_out       [count][n], rbc_dev_verify's valid[]
+ *   values_out      [count][value_pitch]: k*shard_lens[i] bytes, then zeros
+ *   digests_out     [count][32] (nullable) and status_out [count], as
+ *                   rbc_interpolate_batch defines them, over the proven rows.
+ * An instance with messages of verdict 2 or 3 is completed by the caller: run
+ * those messages through the host decoder and the instance through
+ * rbc_interpolate_batch.
+ * Every argument is checked before any device work, and RBC_ERR_INVALID_ARG
+ * enqueues nothing: null pointers; count > max_count, msgs > max_msgs,
+ * ring_bytes > max_ring_bytes; offs[m] % 16 != 0 or offs[m] +
+ * round_up(lens[m], 16) > ring_bytes; inst[m] >= count, idx[m] >= n; two
+ * messages with the same (inst, idx); shard_lens[i] == 0 or > shard_pitch;
+ * value_pitch < k * max shard_lens[i].
+ * Asynchronous: the outputs and the ring belong to the call until
+ * rbc_wire_receive_wait(ticket) returns.  One submission is in flight at a
+ * time: a second rbc_wire_receive on the same receiver first completes the
+ * one before.  The call uses the context's decode workspace like any
+ * rbc_dev_* caller: while a submission is in flight the context must not run
+ * rbc_dev_verify, rbc_dev_interpolate or rbc_dev_receive_step work on another
+ * stream. */
+int rbc_wire_receive(rbc_wire_receiver *rcv, int count, int msgs, const uint8_t *ring, size_t ring_bytes,
+                     const uint64_t *offs, const uint32_t *lens, const uint32_t *inst, const uint8_t *idx,
+                     const uint8_t *roots, const size_t *shard_lens, uint8_t *verdict_out, uint8_t *types_out,
+                     uint8_t *valid_out, uint8_t *values_out, size_t value_pitch, uint8_t *digests_out,
+                     int32_t *status_out, uint64_t *ticket);
+int rbc_wire_receive_wait(rbc_wire_receiver *rcv, uint64_t ticket);
+int rbc_wire_receive_poll(rbc_wire_receiver *rcv, uint64_t ticket, int *done);
+
 /* ---- RBC instance (one proposer's broadcast, seen at one node) ----------- */
 typedef struct rbc_node rbc_node;
 /* NewRBC (rbc/rbc.go:38). */

@@ -11,14 +11,21 @@ pb.Message bytes in a pinned ring (a pass-through gRPC codec's view).
   K  the unmarshal kernel alone on a device-resident ring, from events, beside
      its byte floor (bytes read + written over the HBM rate DESIGN.md uses).
 
+  C  today's composition to delivered values: rbc_wire_validate, the host
+     reads the verdicts and groups the kept rows by instance, then
+     rbc_interpolate_batch_kept.
+  R  rbc_wire_receive: the same ring to the same values in one submission.
+
 Every leg is a child process of its own under its own time limit; the parent
 stops at the first one that fails.  Each leg runs --warmup (>= 2) epochs, then
 --epochs (>= 5) timed ones, and reports the median and the min-max spread.  The
 epoch is seeded, so the legs see the same bytes, and A's and B's verdicts must
-be identical (a digest of them is compared).  About 1 % of the messages carry
-one corrupted shard character, so both verdict values occur.
+be identical (a digest of them is compared), and so must C's and R's statuses
+and value bytes.  About 1 % of the messages carry one corrupted shard
+character, so both verdict values occur.
 
-  python tools/wire_rx_bench.py --out profiles/wire_rx/c2.json
+  python tools/wire_rx_bench.py --legs A,B,K --out profiles/wire_rx/c2.json
+  python tools/wire_rx_bench.py --legs C,R --out profiles/wire_rx/c2_receive.json
 """
 import argparse
 import ctypes
@@ -35,6 +42,10 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 HBM_BPS = 8e12  # the roofline's HBM rate
 THREADS = 16
+
+
+NAMES = {"A": "A_parent_decode_then_validate_packed_keep", "B": "B_wire_validate", "K": "K_unmarshal_kernel",
+         "C": "C_wire_validate_then_interpolate_kept", "R": "R_wire_receive"}
 
 
 def rup(x, a):
@@ -81,7 +92,10 @@ def build_epoch(ca, ctx, a):
         r2[m, at] = ord("A") if r2[m, at] != ord("A") else ord("B")
     offs = np.arange(count, dtype=np.uint64) * slot
     lens = np.full(count, mlen, np.uint32)
+    inst = np.repeat(np.arange(a.instances, dtype=np.uint32), a.echoes)
+    roots = np.ascontiguousarray(c["roots"])[np.arange(a.instances) % distinct]
     return {"ring": ring, "offs": offs, "lens": lens, "idx": idx, "count": count, "S": S, "mlen": mlen,
+            "inst": inst, "roots": np.ascontiguousarray(roots), "instances": a.instances,
             "wire_bytes": int(count) * mlen, "shard_bytes": int(count) * S}
 
 
@@ -204,11 +218,71 @@ def leg_k(ca, ctx, e, a):
             "achieved_TBps": (read + written) / med / 1e12}
 
 
+def result_digest(status, values, used):
+    """Statuses and the value bytes of the delivered instances."""
+    import numpy as np
+    h = hashlib.sha256(np.ascontiguousarray(status, np.int32).tobytes())
+    for i in np.nonzero(np.asarray(status) == 0)[0]:
+        h.update(values[i, :used].tobytes())
+    return h.hexdigest()
+
+
+def leg_c(ca, ctx, e, a):
+    import numpy as np
+    count, S, I, n, k = e["count"], e["S"], e["instances"], ctx.n, ctx.k
+    pitch = rup(S, 64)
+    rx = ca.WireRx(ctx, count, e["ring"].nbytes, pitch)
+    keep = ca.DeviceBuffer(count * pitch)
+    values = ca.pinned_empty((I, k * S))
+    addr = np.uint64(keep.value) + np.arange(count, dtype=np.uint64) * np.uint64(pitch)
+    inst, idx = e["inst"].astype(np.int64), e["idx"].astype(np.int64)
+    got, res, group_s = {}, {}, []
+
+    def epoch():
+        got.update(rx.validate(e["ring"], e["offs"], e["lens"], e["idx"], keep))
+        t0 = time.perf_counter()  # the host's turn: verdicts -> the [instances][n] table of kept rows
+        use = (got["verdict"] == 1) & (got["shard_lens"] == S) & (got["roots"] == e["roots"][inst]).all(axis=1)
+        rows = np.zeros((I, n), np.uint64)
+        leaves = np.zeros((I, n, 32), np.uint8)
+        rows[inst[use], idx[use]] = addr[use]
+        leaves[inst[use], idx[use]] = got["leaves"][use]
+        group_s.append(time.perf_counter() - t0)
+        res.update(ctx.interpolate_kept_submit(rows, [S] * I, e["roots"], leaves=leaves, values_out=values).wait())
+
+    ts = timed(epoch, a.warmup, a.epochs)
+    r = stats(ts, e["shard_bytes"])
+    r.update(result_sha256=result_digest(res["status"], res["values"], k * S), delivered=int((res["status"] == 0).sum()),
+             proven=int((got["verdict"] == 1).sum()), host_grouping_median_s=statistics.median(group_s[a.warmup:]),
+             h2d_bytes=int(e["ring"].nbytes))
+    rx.close()
+    return r
+
+
+def leg_r(ca, ctx, e, a):
+    count, S, I, k = e["count"], e["S"], e["instances"], ctx.k
+    rcv = ca.WireReceiver(ctx, I, count, e["ring"].nbytes, rup(S, 64))
+    values = ca.pinned_empty((I, k * S))
+    got = {}
+
+    def epoch():
+        got.update(rcv.receive(e["ring"], e["offs"], e["lens"], e["inst"], e["idx"], e["roots"], [S] * I,
+                               values_out=values))
+
+    ts = timed(epoch, a.warmup, a.epochs)
+    assert (got["verdict"] < 2).all(), "a message of the project's own encoder fell back"
+    r = stats(ts, e["shard_bytes"])
+    r.update(result_sha256=result_digest(got["status"], got["values"], k * S),
+             delivered=int((got["status"] == 0).sum()), proven=int((got["verdict"] == 1).sum()),
+             h2d_bytes=int(e["ring"].nbytes))
+    rcv.close()
+    return r
+
+
 def child(a):
     import cleisthenes_amd as ca
     ctx = ca.Context(a.n, a.f)
     e = build_epoch(ca, ctx, a)
-    r = {"A": leg_a, "B": leg_b, "K": leg_k}[a.leg](ca, ctx, e, a)
+    r = {"A": leg_a, "B": leg_b, "K": leg_k, "C": leg_c, "R": leg_r}[a.leg](ca, ctx, e, a)
     r.update(leg=a.leg, count=e["count"], shard_len=e["S"], message_len=e["mlen"], wire_bytes=e["wire_bytes"],
              shard_bytes=e["shard_bytes"], library=os.path.relpath(ca.rbc.library_path(), ROOT))
     print("WIRE_RX_LEG " + json.dumps(r), flush=True)
@@ -227,14 +301,18 @@ def main():
     p.add_argument("--seed", type=int, default=20261019)
     p.add_argument("--leg-timeout", type=int, default=240, help="seconds per leg")
     p.add_argument("--out", default=None)
-    p.add_argument("--leg", choices=["A", "B", "K"], default=None, help=argparse.SUPPRESS)
+    p.add_argument("--legs", default="A,B,K", help="comma-separated legs to run, of A B K C R")
+    p.add_argument("--leg", choices=list(NAMES), default=None, help=argparse.SUPPRESS)
     a = p.parse_args()
     if a.warmup < 2 or a.epochs < 5:
         p.error("at least 2 warm-up and 5 timed epochs")
     if a.leg:
         return child(a)
+    want = [x for x in a.legs.split(",") if x]
+    if not want or any(x not in NAMES for x in want):
+        p.error("--legs takes a comma-separated list of " + " ".join(NAMES))
     legs = {}
-    for leg in ("A", "B", "K"):
+    for leg in want:
         cmd = [sys.executable, os.path.abspath(__file__), "--leg", leg] + \
             [x for k in ("n", "f", "instances", "echoes", "shard_len", "distinct", "warmup", "epochs", "seed")
              for x in ("--" + k.replace("_", "-"), str(getattr(a, k)))]
@@ -248,12 +326,21 @@ def main():
             sys.stderr.write(r.stdout[-2000:] + r.stderr[-4000:])
             sys.exit(f"leg {leg} failed (exit {r.returncode}); stopping")
         legs[leg] = json.loads(line[-1][len("WIRE_RX_LEG "):])
-    same = legs["A"]["verdict_sha256"] == legs["B"]["verdict_sha256"]
     res = {"bench": "wire_rx", "geometry": {"n": a.n, "f": a.f, "instances": a.instances, "echoes": a.echoes,
                                             "shard_len": a.shard_len}, "threads": THREADS, "warmup": a.warmup,
-           "epochs": a.epochs, "verdicts_identical": same, "A_parent_decode_then_validate_packed_keep": legs["A"],
-           "B_wire_validate": legs["B"], "K_unmarshal_kernel": legs["K"],
-           "B_over_A_median": legs["A"]["median_s"] / legs["B"]["median_s"]}
+           "epochs": a.epochs}
+    same = True
+    if "A" in legs and "B" in legs:
+        same = legs["A"]["verdict_sha256"] == legs["B"]["verdict_sha256"]
+        res.update(verdicts_identical=same, B_over_A_median=legs["A"]["median_s"] / legs["B"]["median_s"])
+    if "C" in legs and "R" in legs:
+        c, r = legs["C"], legs["R"]
+        res.update(results_identical=c["result_sha256"] == r["result_sha256"],
+                   R_over_C_median=c["median_s"] / r["median_s"],
+                   R_vs_C="win" if r["max_s"] < c["min_s"] else "loss" if r["min_s"] > c["max_s"] else "tie")
+        same = same and res["results_identical"]
+    for leg in want:
+        res[NAMES[leg]] = legs[leg]
     text = json.dumps(res, indent=1)
     if a.out:
         os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
@@ -261,7 +348,7 @@ def main():
             fh.write(text + "\n")
     print(text)
     if not same:
-        sys.exit("the two legs' verdicts differ")
+        sys.exit("two legs that must agree gave different results")
 
 
 if __name__ == "__main__":
