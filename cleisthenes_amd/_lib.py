@@ -200,6 +200,16 @@ _SIGS = {
                                  POINTER(c_uint64)]),
     "rbc_wire_receive_wait": (c_int, [c_void_p, c_uint64]),
     "rbc_wire_receive_poll": (c_int, [c_void_p, c_uint64, POINTER(c_int)]),
+    # the binary VAL / ECHO payload codec (RBC_HAS_WIRE_BINARY)
+    "rbc_bin_encode_val": (c_size_t, [c_void_p, c_size_t, c_void_p, c_size_t, c_void_p, c_size_t, c_void_p,
+                                      c_size_t]),
+    "rbc_bin_decode_val": (c_int, [c_void_p, c_size_t, c_void_p, c_void_p, c_size_t, szp, c_void_p, c_size_t, szp]),
+    "rbc_payload_decode_val": (c_int, [c_void_p, c_size_t, c_void_p, c_void_p, c_size_t, szp, c_void_p, c_size_t,
+                                       szp]),
+    "rbc_val_message_size_codec": (c_size_t, [c_int, c_int, c_uint32, c_uint32, c_int]),
+    "rbc_ctx_set_wire_codec": (c_int, [c_void_p, c_int]),
+    "rbc_ctx_wire_codec": (c_int, [c_void_p, POINTER(c_int)]),
+    "rbc_node_set_wire_codec": (c_int, [c_void_p, c_int]),
     # parity-only shard commit (RBC_HAS_SHARD_COMMIT_PARITY)
     "rbc_dev_shard_commit_parity": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_uint64, c_void_p, c_uint32,
                                             c_void_p, c_void_p, c_uint32, c_void_p, c_void_p, c_void_p, c_void_p]),
@@ -219,18 +229,23 @@ _SIGS = {
 }
 
 # Additions made at an unchanged ABI version are detected by symbol, as their
-# header macros say (RBC_HAS_WIRE_RX, RBC_HAS_WIRE_RECEIVE): another build of
+# header macros say (RBC_HAS_WIRE_RX, RBC_HAS_WIRE_RECEIVE, RBC_HAS_WIRE_BINARY): another build of
 # ABI 7 (RBC_GPU_LIB) may lack them.  They are then left unbound, and using one
 # raises.
 _BY_SYMBOL = ("rbc_dev_unmarshal_val", "rbc_wire_rx_create", "rbc_wire_rx_destroy", "rbc_wire_validate",
               "rbc_wire_wait", "rbc_wire_poll")
 _BY_SYMBOL_RECEIVE = ("rbc_dev_unmarshal_echo", "rbc_wire_receiver_create", "rbc_wire_receiver_destroy",
                       "rbc_wire_receive", "rbc_wire_receive_wait", "rbc_wire_receive_poll")
+_BY_SYMBOL_BINARY = ("rbc_bin_encode_val", "rbc_bin_decode_val", "rbc_payload_decode_val",
+                     "rbc_val_message_size_codec", "rbc_ctx_set_wire_codec", "rbc_ctx_wire_codec",
+                     "rbc_node_set_wire_codec")
 HAS_WIRE_RX = all(hasattr(lib, _name) for _name in _BY_SYMBOL)
 HAS_WIRE_RECEIVE = all(hasattr(lib, _name) for _name in _BY_SYMBOL_RECEIVE)
+HAS_WIRE_BINARY = all(hasattr(lib, _name) for _name in _BY_SYMBOL_BINARY)
 
 for _name, (_res, _args) in _SIGS.items():
-    if (_name in _BY_SYMBOL and not HAS_WIRE_RX) or (_name in _BY_SYMBOL_RECEIVE and not HAS_WIRE_RECEIVE):
+    if ((_name in _BY_SYMBOL and not HAS_WIRE_RX) or (_name in _BY_SYMBOL_RECEIVE and not HAS_WIRE_RECEIVE)
+            or (_name in _BY_SYMBOL_BINARY and not HAS_WIRE_BINARY)):
         continue
     _fn = getattr(lib, _name)
     _fn.restype = _res
@@ -245,6 +260,12 @@ def require_wire_rx() -> None:
 def require_wire_receive() -> None:
     if not HAS_WIRE_RECEIVE:
         raise ImportError(f"{LIB_PATH} has no wire receiver (RBC_HAS_WIRE_RECEIVE): rbc_wire_receive missing")
+
+
+def require_wire_binary() -> None:
+    if not HAS_WIRE_BINARY:
+        raise ImportError(f"{LIB_PATH} has no binary payload codec (RBC_HAS_WIRE_BINARY): "
+                          "rbc_ctx_set_wire_codec missing")
 
 
 def header_functions(path: str = None):
@@ -283,6 +304,8 @@ RBC_MSG_VAL, RBC_MSG_ECHO, RBC_MSG_READY = 0, 1, 2
 RBC_WIRE_OK, RBC_WIRE_FALLBACK = 0, 1
 # rbc_dev_unmarshal_echo adds (RBC_HAS_WIRE_RECEIVE)
 RBC_WIRE_OTHER_ROOT, RBC_WIRE_OTHER_LEN = 2, 3
+# payload codec of the wire path (RBC_HAS_WIRE_BINARY)
+RBC_WIRE_CODEC_JSON, RBC_WIRE_CODEC_BINARY = 0, 1
 
 
 class RBCError(Exception):

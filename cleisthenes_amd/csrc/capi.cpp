@@ -190,6 +190,8 @@ struct rbc_ctx {
     // the receive step's root recheck: RBC_RECHECK_REUSE (default: over the
     // nodes ECHO verify established) or RBC_RECHECK_FULL (the whole tree)
     int recheck = RBC_RECHECK_REUSE;
+    // payload codec of the wire entry points (rbc_ctx_set_wire_codec), read at submission
+    int wire_codec = RBC_WIRE_CODEC_JSON;
     int gemv_prio() const { return gemv_prio_ < 0 ? tx_prio : gemv_prio_; }
     int reencode_prio() const { return reencode_prio_ < 0 ? tx_prio : reencode_prio_; }
     std::vector<uint8_t> h_M;      // n x k encode matrix
@@ -1256,6 +1258,18 @@ int rbc_ctx_codec(const rbc_ctx *c, int *codec) {
     return RBC_OK;
 }
 
+int rbc_ctx_set_wire_codec(rbc_ctx *c, int codec) {
+    if (!c || (codec != RBC_WIRE_CODEC_JSON && codec != RBC_WIRE_CODEC_BINARY)) return RBC_ERR_INVALID_ARG;
+    c->wire_codec = codec;
+    return RBC_OK;
+}
+
+int rbc_ctx_wire_codec(const rbc_ctx *c, int *codec) {
+    if (!c || !codec) return RBC_ERR_INVALID_ARG;
+    *codec = c->wire_codec;
+    return RBC_OK;
+}
+
 int rbc_ctx_encode_matrix(const rbc_ctx *c, uint8_t *out) {
     if (!c || !out) return RBC_ERR_INVALID_ARG;
     memcpy(out, c->h_M.data(), c->h_M.size());
@@ -1428,6 +1442,13 @@ size_t rbc_val_message_size(int n, uint32_t shard_len, uint32_t index, int type)
     return rbc_val_message_bytes(n, d, shard_len, index, type);
 }
 
+size_t rbc_val_message_size_codec(int codec, int n, uint32_t shard_len, uint32_t index, int type) {
+    if (n < 1) return 0;
+    int d = 0;
+    while ((1 << d) < n) ++d;
+    return rbc_val_message_bytes_codec(codec, n, d, shard_len, index, type);
+}
+
 int rbc_dev_marshal_val(rbc_ctx *c, void *stream, int count, int type, const uint8_t *shards,
                         uint32_t shard_pitch, const uint32_t *shard_lens, uint32_t uniform_shard_len,
                         const uint8_t *branches, const uint8_t *roots, uint8_t *out, uint64_t out_pitch,
@@ -1436,7 +1457,8 @@ int rbc_dev_marshal_val(rbc_ctx *c, void *stream, int count, int type, const uin
     if (count == 0) return RBC_OK;
     if (!shards || !roots || !out || (c->depth && !branches)) return RBC_ERR_INVALID_ARG;
     if (!shard_lens && (uniform_shard_len == 0 || uniform_shard_len > shard_pitch ||
-                        out_pitch < rbc_val_message_bytes(c->n, c->depth, uniform_shard_len, 0, type)))
+                        out_pitch < rbc_val_message_bytes_codec(c->wire_codec, c->n, c->depth, uniform_shard_len, 0,
+                                                                type)))
         return RBC_ERR_INVALID_ARG;
     RBC_HIP(hipSetDevice(c->device));
     WireArgs a{};
@@ -1454,6 +1476,7 @@ int rbc_dev_marshal_val(rbc_ctx *c, void *stream, int count, int type, const uin
     a.out = out;
     a.out_pitch = out_pitch;
     a.out_lens = out_lens;
+    a.codec = c->wire_codec;
     RBC_HIP(rbc_launch_marshal_val(a, as_stream(stream)));
     return RBC_OK;
 }
@@ -1918,9 +1941,10 @@ int rbc_shard_commit_val(rbc_ctx *c, int count, const uint8_t *const *values, co
         Smax = std::max(Smax, (value_lens[i] + c->k - 1) / c->k);
     }
     const int d = c->depth, n = c->n;
-    const size_t need = round_up(std::max(rbc_val_message_bytes(n, d, (uint32_t)Smax, 0, RBC_MSG_VAL),
-                                          rbc_val_message_bytes(n, d, (uint32_t)Smax, (uint32_t)(n - 1),
-                                                                RBC_MSG_VAL)),
+    const int codec = c->wire_codec;
+    const size_t need = round_up(std::max(rbc_val_message_bytes_codec(codec, n, d, (uint32_t)Smax, 0, RBC_MSG_VAL),
+                                          rbc_val_message_bytes_codec(codec, n, d, (uint32_t)Smax, (uint32_t)(n - 1),
+                                                                      RBC_MSG_VAL)),
                                  16);
     if (msg_pitch < need || msg_pitch % 16) return RBC_ERR_INVALID_ARG;
     const size_t dpitch = round_up(Smax, 128);
@@ -1985,6 +2009,7 @@ int rbc_shard_commit_val(rbc_ctx *c, int count, const uint8_t *const *values, co
     a.out = d_msgs;
     a.out_pitch = msg_pitch;
     a.out_lens = d_mlens;
+    a.codec = codec;
     RBC_HIP(rbc_launch_marshal_val(a, st));
     // one D2H of the finished messages: straight into a pinned ring, else
     // through HIP's staging (pageable); deferred behind the next submission's H2D

@@ -107,3 +107,23 @@ inline size_t rbc_val_message_bytes(int n, int depth, uint32_t S, uint32_t index
     const uint64_t R = 1 + vl(J) + J + (type ? 2 : 0);
     return (size_t)(1 + vl(R) + R);
 }
+
+// The same for a payload codec (include/rbc_protocol.h: 0 JSON, 1 binary, whose
+// payload is 40 + branch + S bytes; the mirror of wire.hip's bin_layout().total);
+// 0 for an unknown codec.
+inline size_t rbc_val_message_bytes_codec(int codec, int n, int depth, uint32_t S, uint32_t index, int type) {
+    if (codec == 0) return rbc_val_message_bytes(n, depth, S, index, type);
+    if (codec != 1) return 0;
+    auto vl = [](uint64_t v) {
+        uint64_t l = 1;
+        while (v >= 0x80) {
+            v >>= 7;
+            ++l;
+        }
+        return l;
+    };
+    const bool empty0 = depth > 0 && (int)(index ^ 1u) >= n;
+    const uint64_t J = 40 + 32u * (uint64_t)(depth - (empty0 ? 1 : 0)) + S;
+    const uint64_t R = 1 + vl(J) + J + (type ? 2 : 0);
+    return (size_t)(1 + vl(R) + R);
+}

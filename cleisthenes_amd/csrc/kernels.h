@@ -224,9 +224,16 @@ struct WireArgs {
     uint8_t *out;
     uint64_t out_pitch;  // % 16 == 0
     uint32_t *out_lens;  // [count*n], nullable
+    int codec;           // payload codec (include/rbc_protocol.h): 0 JSON, 1 binary
 };
 hipError_t rbc_launch_marshal_val(const WireArgs &a, hipStream_t st);
 
+// The three wire launchers choose their kernel by the `codec` field of their
+// arguments (include/rbc_protocol.h, RBC_HAS_WIRE_BINARY): 0 the Go-JSON
+// payload, 1 the binary one (marshal_val_bin_kernel, unmarshal_val_bin_kernel,
+// unmarshal_echo_bin_kernel), with the same output contracts; any other value
+// is hipErrorInvalidValue.
+//
 // Per-message status of the unmarshal kernel (include/rbc_protocol.h)
 enum { WIRE_OK = 0, WIRE_FALLBACK = 1, WIRE_OTHER_ROOT = 2, WIRE_OTHER_LEN = 3 };
 
@@ -249,6 +256,7 @@ struct WireRxArgs {
     uint8_t *roots;        // [count][32]
     uint8_t *types;        // [count]
     int32_t *status;       // [count] WIRE_OK / WIRE_FALLBACK
+    int codec;             // payload codec: 0 JSON, 1 binary
 };
 hipError_t rbc_launch_unmarshal_val(const WireRxArgs &a, hipStream_t st);
 
@@ -279,6 +287,7 @@ struct WireEchoArgs {
     uint8_t *present;            // [count][n]: 1 written for WIRE_OK, else untouched
     int32_t *msg_status;         // [msgs]
     uint8_t *types;              // [msgs], nullable
+    int codec;                   // payload codec: 0 JSON, 1 binary
 };
 hipError_t rbc_launch_unmarshal_echo(const WireEchoArgs &a, hipStream_t st);
 

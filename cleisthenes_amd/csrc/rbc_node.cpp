@@ -448,6 +448,41 @@ size_t emit(const std::string &s, uint8_t *out, size_t cap) {
 }
 
 // ---------------------------------------------------------------------------
+// The binary VAL / ECHO payload (include/rbc_protocol.h, version 1):
+// magic, version, L, 0, S as u32 LE, root, L branch entries, the shard
+// ---------------------------------------------------------------------------
+constexpr size_t kBinHead = 40;  // the 8 header bytes and the root
+
+bool bin_fits(size_t rl, size_t bl, size_t kl) {
+    return rl == 32 && bl % 32 == 0 && bl / 32 <= 255 && kl <= 0xffffffffu;
+}
+
+std::string bin_val(const uint8_t *root, const uint8_t *branch, size_t bl, const uint8_t *block, size_t kl) {
+    std::string s;
+    s.reserve(kBinHead + bl + kl);
+    s.push_back((char)RBC_BIN_MAGIC);
+    s.push_back((char)RBC_BIN_VERSION);
+    s.push_back((char)(bl / 32));
+    s.push_back(0);
+    for (int b = 0; b < 4; ++b) s.push_back((char)((uint32_t)kl >> (8 * b)));
+    s.append((const char *)root, 32);
+    if (bl) s.append((const char *)branch, bl);
+    if (kl) s.append((const char *)block, kl);
+    return s;
+}
+
+// the branch and shard extents of a well-formed payload
+bool bin_parse(const uint8_t *p, size_t len, size_t *bl, size_t *kl) {
+    if (len < kBinHead || p[0] != RBC_BIN_MAGIC || p[1] != RBC_BIN_VERSION || p[3] != 0) return false;
+    const size_t L = p[2];
+    const size_t S = (size_t)p[4] | (size_t)p[5] << 8 | (size_t)p[6] << 16 | (size_t)p[7] << 24;
+    if (len - kBinHead < 32 * L || len - kBinHead - 32 * L != S) return false;
+    *bl = 32 * L;
+    *kl = S;
+    return true;
+}
+
+// ---------------------------------------------------------------------------
 // instance state
 // ---------------------------------------------------------------------------
 enum OpKind { OP_SHARD, OP_VAL, OP_ECHO, OP_INTERP };
@@ -505,6 +540,13 @@ struct rbc_node {
     std::deque<std::unique_ptr<Op>> ops;
     std::deque<Out> outq;
     int rejected = 0;
+    int wire_codec = RBC_WIRE_CODEC_JSON;  // of the VAL / ECHO this node emits
+
+    std::string val_payload(const uint8_t *root, const uint8_t *branch, size_t bl, const uint8_t *block,
+                            size_t kl) const {
+        return wire_codec == RBC_WIRE_CODEC_BINARY ? bin_val(root, branch, bl, block, kl)
+                                                   : json_val(root, 32, branch, bl, block, kl);
+    }
 
     RootState &state(const std::string &root) {
         RootState &s = roots[root];
@@ -572,8 +614,8 @@ struct rbc_node {
     // finds them again for the interpolate)
     void on_val(Request &r) {
         send(-1, RBC_MSG_ECHO,
-             json_val((const uint8_t *)r.root.data(), r.root.size(), (const uint8_t *)r.branch.data(),
-                      r.branch.size(), (const uint8_t *)r.block[0].data(), r.block[0].size()));
+             val_payload((const uint8_t *)r.root.data(), (const uint8_t *)r.branch.data(), r.branch.size(),
+                         (const uint8_t *)r.block[0].data(), r.block[0].size()));
         on_echo(self, r.root, std::move(r.block[0]));
     }
 
@@ -646,8 +688,8 @@ struct rbc_node {
                         own = std::move(r);
                     else
                         send(j, RBC_MSG_VAL,
-                             json_val((const uint8_t *)r.root.data(), 32, (const uint8_t *)r.branch.data(),
-                                      r.branch.size(), (const uint8_t *)r.block[0].data(), op.S));
+                             val_payload((const uint8_t *)r.root.data(), (const uint8_t *)r.branch.data(),
+                                         r.branch.size(), (const uint8_t *)r.block[0].data(), op.S));
                 }
                 on_val(own);
                 break;
@@ -718,6 +760,44 @@ int rbc_json_decode_val(const uint8_t *json, size_t len, uint8_t *root_out, uint
     return RBC_OK;
 }
 
+size_t rbc_bin_encode_val(const uint8_t *root, size_t root_len, const uint8_t *branch, size_t branch_len,
+                          const uint8_t *block, size_t block_len, uint8_t *out, size_t cap) {
+    if (!branch) branch_len = 0;
+    if (!block) block_len = 0;
+    if (!root || !bin_fits(root_len, branch_len, block_len)) return 0;
+    return emit(bin_val(root, branch, branch_len, block, block_len), out, cap);
+}
+
+int rbc_bin_decode_val(const uint8_t *payload, size_t len, uint8_t *root_out, uint8_t *branch_out, size_t branch_cap,
+                       size_t *branch_len, uint8_t *block_out, size_t block_cap, size_t *block_len) {
+    if ((!payload && len) || !root_out || !branch_len || !block_len) return RBC_ERR_INVALID_ARG;
+    size_t bl, kl;
+    if (!bin_parse(payload, len, &bl, &kl)) return RBC_ERR_PROTOCOL;
+    *branch_len = bl;
+    *block_len = kl;
+    if (bl > branch_cap || kl > block_cap) return RBC_ERR_INVALID_ARG;
+    memcpy(root_out, payload + 8, 32);
+    if (branch_out && bl) memcpy(branch_out, payload + kBinHead, bl);
+    if (block_out && kl) memcpy(block_out, payload + kBinHead + bl, kl);
+    return RBC_OK;
+}
+
+int rbc_payload_decode_val(const uint8_t *payload, size_t len, uint8_t *root_out, uint8_t *branch_out,
+                           size_t branch_cap, size_t *branch_len, uint8_t *block_out, size_t block_cap,
+                           size_t *block_len) {
+    if (payload && len && payload[0] == RBC_BIN_MAGIC)
+        return rbc_bin_decode_val(payload, len, root_out, branch_out, branch_cap, branch_len, block_out, block_cap,
+                                  block_len);
+    return rbc_json_decode_val(payload, len, root_out, branch_out, branch_cap, branch_len, block_out, block_cap,
+                               block_len);
+}
+
+int rbc_node_set_wire_codec(rbc_node *node, int codec) {
+    if (!node || (codec != RBC_WIRE_CODEC_JSON && codec != RBC_WIRE_CODEC_BINARY)) return RBC_ERR_INVALID_ARG;
+    node->wire_codec = codec;
+    return RBC_OK;
+}
+
 int rbc_json_decode_ready(const uint8_t *json, size_t len, uint8_t *root_out) {
     if ((!json && len) || !root_out) return RBC_ERR_INVALID_ARG;
     Request r;
@@ -781,7 +861,19 @@ int rbc_node_handle_message(rbc_node *node, int sender, const uint8_t *msg, size
     const uint8_t *pl;
     size_t pll;
     Request r;
-    if (pb_parse(msg, len, &type, &pl, &pll) != RBC_OK || !json_parse(pl, pll, r) || r.root.size() != 32) {
+    bool parsed = pb_parse(msg, len, &type, &pl, &pll) == RBC_OK;
+    if (parsed && node->wire_codec == RBC_WIRE_CODEC_BINARY && type != RBC_MSG_READY && pll &&
+        pl[0] == RBC_BIN_MAGIC) {  // a binary node takes either form (rbc_payload_decode_val's rule)
+        size_t bl, kl;
+        if ((parsed = bin_parse(pl, pll, &bl, &kl))) {
+            r.root.assign((const char *)pl + 8, 32);
+            r.branch.assign((const char *)pl + kBinHead, bl);
+            r.block.emplace_back((const char *)pl + kBinHead + bl, kl);
+        }
+    } else if (parsed) {
+        parsed = json_parse(pl, pll, r) && r.root.size() == 32;
+    }
+    if (!parsed) {
         node->rejected++;
         return RBC_ERR_PROTOCOL;
     }

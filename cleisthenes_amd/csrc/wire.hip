@@ -528,24 +528,338 @@ __global__ __launch_bounds__(256) void unmarshal_echo_kernel(WireEchoArgs a) {
     }
 }
 
+// ---------------------------------------------------------------------------
+// The binary payload codec (include/rbc_protocol.h, RBC_HAS_WIRE_BINARY): the
+// same pb.Message wrapper around
+//   0xB1 0x01 L 0x00 | S as u32 LE | root[32] | branch[32*L] | shard[S]
+// so root, branch and shard are raw bytes and the three kernels below are
+// phase-shifted copies: the runs start 8 + 32*k bytes behind the wrapper's
+// header, hence all at one phase of the 16-byte chunks, and that phase is
+// wave-uniform.  Same launch shape and the same output contracts as the JSON
+// kernels above; no LDS.
+// ---------------------------------------------------------------------------
+
+// Shape of the binary message of an S-byte shard with L branch entries.
+struct BinLayout {
+    uint32_t total, hdr;  // message bytes; 0x1a varint(R) 0x0a varint(J)
+    uint32_t R, J, S, L;
+    uint32_t root_off, br_off, blk_off, type_off;  // type_off: the end of the shard
+};
+
+__device__ __forceinline__ BinLayout bin_layout(uint32_t S, uint32_t L, int type) {
+    BinLayout c;
+    c.S = S;
+    c.L = L;
+    c.J = 40 + 32 * L + S;
+    c.R = 1 + varint_len(c.J) + c.J + (type ? 2 : 0);
+    c.hdr = 1 + varint_len(c.R) + 1 + varint_len(c.J);
+    c.total = 1 + varint_len(c.R) + c.R;
+    c.root_off = c.hdr + 8;
+    c.br_off = c.root_off + 32;
+    c.blk_off = c.br_off + 32 * L;
+    c.type_off = c.blk_off + S;
+    return c;
+}
+
+// byte p < hdr + 8 of the message: the wrapper's header and the payload's
+__device__ __forceinline__ uint32_t bin_head_byte(const BinLayout &c, uint32_t p) {
+    const uint32_t vr = varint_len(c.R);
+    if (p == 0) return 0x1a;
+    if (p < 1 + vr) return varint_byte(c.R, p - 1);
+    if (p == 1 + vr) return 0x0a;
+    if (p < c.hdr) return varint_byte(c.J, p - 2 - vr);
+    const uint32_t k = p - c.hdr;
+    return k == 0 ? 0xB1u : k == 1 ? 0x01u : k == 2 ? c.L : k == 3 ? 0u : (c.S >> (8 * (k - 4))) & 0xffu;
+}
+
+// byte p of the message (the slow, per-byte path of the marshal kernel)
+__device__ uint32_t bin_msg_byte(const BinLayout &c, uint32_t p, const uint8_t *root, const uint8_t *br,
+                                 const uint8_t *blk) {
+    if (p >= c.total) return 0;
+    if (p < c.root_off) return bin_head_byte(c, p);
+    if (p < c.br_off) return root[p - c.root_off];
+    if (p < c.blk_off) return br[p - c.br_off];
+    if (p < c.type_off) return blk[p - c.blk_off];
+    return p == c.type_off ? 0x10u : 0x01u;  // only ECHO has bytes here
+}
+
+// bytes [ph, ph + 16) of the 32 bytes lo:hi (ph < 16, wave-uniform)
+__device__ __forceinline__ uint4 shift16(const uint4 lo, const uint4 hi, uint32_t ph) {
+    const uint32_t c[8] = {lo.x, lo.y, lo.z, lo.w, hi.x, hi.y, hi.z, hi.w};
+    const uint32_t dw = ph >> 2, a = ph & 3;
+    uint32_t e[5];
+#pragma unroll
+    for (int k = 0; k < 5; ++k) e[k] = dw == 0 ? c[k] : dw == 1 ? c[k + 1] : dw == 2 ? c[k + 2] : c[k + 3];
+    return make_uint4(__builtin_amdgcn_alignbyte(e[1], e[0], a), __builtin_amdgcn_alignbyte(e[2], e[1], a),
+                      __builtin_amdgcn_alignbyte(e[3], e[2], a), __builtin_amdgcn_alignbyte(e[4], e[3], a));
+}
+
+// the first `keep` (< 16) bytes of v, zeros behind them
+__device__ __forceinline__ uint4 keep_bytes(uint4 v, uint32_t keep) {
+    uint32_t d[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+    for (uint32_t w = 0; w < 4; ++w) {
+        const uint32_t k = keep > 4 * w ? keep - 4 * w : 0u;
+        if (k < 4) d[w] &= (1u << (8 * k)) - 1u;
+    }
+    return make_uint4(d[0], d[1], d[2], d[3]);
+}
+
+// 16 bytes from src, which may sit at any byte: the 4 or 5 aligned dwords that
+// hold them (the last one holds src[15], so at most 3 bytes behind it are read)
+__device__ __forceinline__ uint4 load16_any(const uint8_t *src) {
+    const uintptr_t u = reinterpret_cast<uintptr_t>(src);
+    const uint32_t a = (uint32_t)(u & 3);
+    const uint32_t *s32 = reinterpret_cast<const uint32_t *>(u - a);
+    const uint32_t d0 = s32[0], d1 = s32[1], d2 = s32[2], d3 = s32[3], d4 = a ? s32[4] : 0u;
+    return make_uint4(__builtin_amdgcn_alignbyte(d1, d0, a), __builtin_amdgcn_alignbyte(d2, d1, a),
+                      __builtin_amdgcn_alignbyte(d3, d2, a), __builtin_amdgcn_alignbyte(d4, d3, a));
+}
+
+// one wave per message; 4 waves (messages) per block
+__global__ __launch_bounds__(256) void marshal_val_bin_kernel(WireArgs a) {
+    const uint32_t msg = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (msg >= (uint32_t)a.count * (uint32_t)a.n) return;
+    const uint32_t lane = threadIdx.x & 63;
+    const uint32_t inst = msg / a.n, j = msg - inst * a.n;
+    const uint32_t S = a.lens ? a.lens[inst] : a.uniform_len;
+    const bool empty0 = a.depth > 0 && (int)(j ^ 1u) >= a.n;
+    const BinLayout c = bin_layout(S, a.depth - (empty0 ? 1 : 0), a.type);
+    const uint8_t *root = a.roots + (size_t)inst * 32;
+    const uint8_t *br = a.branches + ((size_t)inst * a.n + j) * a.depth * 32u + (empty0 ? 32u : 0u);
+    const uint8_t *blk = a.shards + (size_t)inst * a.inst_pitch + (size_t)j * a.row_pitch;
+    uint8_t *out = a.out + (size_t)msg * a.out_pitch;
+    const uint32_t nchunks = (c.total + 15) >> 4;
+    for (uint32_t q = lane; q < nchunks; q += 64) {
+        const uint32_t p = q << 4;
+        uint4 v;
+        // a chunk wholly inside one run is one shifted copy; the few that hold
+        // the header, a run's border or the message's end go byte by byte
+        if (p >= c.blk_off && p + 16 <= c.type_off) {
+            v = load16_any(blk + (p - c.blk_off));
+        } else if (p >= c.br_off && p + 16 <= c.blk_off) {
+            v = load16_any(br + (p - c.br_off));
+        } else if (p >= c.root_off && p + 16 <= c.br_off) {
+            v = load16_any(root + (p - c.root_off));
+        } else {
+            uint32_t d[4];
+#pragma unroll
+            for (int w = 0; w < 4; ++w) {
+                uint32_t x = 0;
+#pragma unroll
+                for (int b = 0; b < 4; ++b) x |= bin_msg_byte(c, p + 4 * w + b, root, br, blk) << (8 * b);
+                d[w] = x;
+            }
+            v = make_uint4(d[0], d[1], d[2], d[3]);
+        }
+        *reinterpret_cast<uint4 *>(out + p) = v;
+    }
+    if (lane == 0 && a.out_lens) a.out_lens[msg] = c.total;
+}
+
+// The receive side.  Every offset comes from lens[i] and idx[i], never from a
+// byte of the message: idx gives L, and for each type the total fixes S,
+//   total = 2 + varint_len(R) + varint_len(J) + 40 + 32*L + S + (type ? 2 : 0),
+// which grows strictly with S, so a type has at most one shape (and none where
+// a varint grows past the total, or below the one-byte shard).  Most totals
+// have one shape per type, (S, VAL) and (S - 2, ECHO).
+__device__ bool bin_rx_shape(uint32_t total, uint32_t L, int type, uint32_t max_S, BinLayout &c) {
+    if (total > 0x7fffffffu) return false;
+    for (uint32_t vj = 1; vj <= 5; ++vj)
+        for (uint32_t vr = vj; vr <= vj + 1; ++vr) {
+            const uint32_t over = 2 + vr + vj + 40 + 32 * L + (type ? 2u : 0u);
+            if (total <= over) continue;  // S >= 1
+            c = bin_layout(total - over, L, type);
+            if (c.total == total) return c.S <= max_S;
+        }
+    return false;
+}
+
+// Does the message carry candidate c's first hdr + 8 bytes (two varints, magic,
+// version, L, reserved byte, S) and, for ECHO, the type field behind the shard?
+// At most 20 + 2 bytes, one per lane; all inside [0, total).
+__device__ __forceinline__ bool bin_matches(const uint8_t *m, const BinLayout &c, int type, uint32_t lane) {
+    bool bad = false;
+    if (lane < c.hdr + 8) bad = m[lane] != bin_head_byte(c, lane);
+    else if (type && lane >= 32 && lane < 34) bad = m[c.type_off + lane - 32] != (lane == 32 ? 0x10u : 0x01u);
+    return !__any(bad);
+}
+
+// Output chunk [o0, o0 + 16) of the run of len bytes at message offset off, as
+// one or two aligned 16-byte loads inside [0, rt) and a shift by the run's
+// phase; zeros from len on.
+__device__ __forceinline__ uint4 bin_chunk16(const uint8_t *m, uint32_t rt, uint32_t off, uint32_t len,
+                                             uint32_t o0) {
+    if (o0 >= len) return make_uint4(0, 0, 0, 0);
+    const uint32_t P = off + o0, A = P & ~15u, ph = P & 15u;
+    const uint4 lo = *reinterpret_cast<const uint4 *>(m + A);
+    uint4 hi = make_uint4(0, 0, 0, 0);
+    if (ph && A + 16 < rt) hi = *reinterpret_cast<const uint4 *>(m + A + 16);
+    const uint4 v = shift16(lo, hi, ph);
+    return len - o0 < 16 ? keep_bytes(v, len - o0) : v;
+}
+
+// one wave per message; 4 waves (messages) per block
+__global__ __launch_bounds__(256) void unmarshal_val_bin_kernel(WireRxArgs a) {
+    const uint32_t i = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (i >= (uint32_t)a.count) return;
+    const uint32_t lane = threadIdx.x & 63;
+    const uint32_t total = a.lens[i], j = a.idx[i];
+    const uint8_t *m = a.msgs + a.offs[i];
+    const bool empty0 = a.depth > 0 && (int)(j ^ 1u) >= a.n;
+    const uint32_t L = a.depth - (empty0 ? 1 : 0);
+    // at most one candidate shape per type, then the one whose header the message carries
+    BinLayout c, c1;
+    int type = 0;
+    bool shaped = false;
+    if (j < (uint32_t)a.n) {
+        shaped = bin_rx_shape(total, L, 0, a.row_pitch, c) && bin_matches(m, c, 0, lane);
+        if (!shaped && bin_rx_shape(total, L, 1, a.row_pitch, c1) && bin_matches(m, c1, 1, lane)) {
+            shaped = true;
+            c = c1;
+            type = 1;
+        }
+    }
+    if (!shaped) {
+        if (lane == 0) {
+            a.status[i] = WIRE_FALLBACK;
+            a.types[i] = 0;
+            a.shard_lens[i] = 0;
+        }
+        return;
+    }
+    // root, branch and shard are any bytes: the message is canonical
+    const uint32_t S = c.S, rt = (total + 15u) & ~15u;
+    const uint32_t nblk = ((S + 63u) & ~63u) >> 4, nbr = 2 * L, nq = nblk + nbr + 2;
+    uint8_t *slot = a.branches + (size_t)i * (a.depth > 1 ? a.depth : 1) * 32u;
+    for (uint32_t q = lane; q < nq; q += 64) {
+        uint32_t off, len, o0;
+        uint8_t *dst;
+        if (q < nblk) {
+            off = c.blk_off, len = S, o0 = q << 4;
+            dst = a.rows + (size_t)i * a.row_pitch;
+        } else if (q < nblk + nbr) {
+            off = c.br_off, len = 32 * L, o0 = (q - nblk) << 4;
+            dst = slot + (empty0 ? 32u : 0u);
+        } else {
+            off = c.root_off, len = 32, o0 = (q - nblk - nbr) << 4;
+            dst = a.roots + (size_t)i * 32;
+        }
+        *reinterpret_cast<uint4 *>(dst + o0) = bin_chunk16(m, rt, off, len, o0);
+    }
+    // the zero slot of an empty level-0 sibling (or of a depth-0 tree)
+    if ((empty0 || a.depth == 0) && lane < 2) reinterpret_cast<uint4 *>(slot)[lane] = make_uint4(0, 0, 0, 0);
+    if (lane == 0) {
+        a.status[i] = WIRE_OK;
+        a.types[i] = (uint8_t)type;
+        a.shard_lens[i] = S;
+    }
+}
+
+// unmarshal_val_bin_kernel for the receiver's batch layout (the contract of
+// unmarshal_echo_kernel).  The instance's shard length is known, so the
+// candidate is fixed before any byte of the message is read: the shape of that
+// length, of whichever type has one.
+// one wave per message; 4 waves (messages) per block
+__global__ __launch_bounds__(256) void unmarshal_echo_bin_kernel(WireEchoArgs a) {
+    const uint32_t i = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (i >= (uint32_t)a.msgs) return;
+    const uint32_t lane = threadIdx.x & 63;
+    const uint32_t total = a.lens[i], j = a.idx[i], in = a.inst[i];
+    const uint8_t *m = a.ring + a.offs[i];
+    const bool empty0 = a.depth > 0 && (int)(j ^ 1u) >= a.n;
+    const uint32_t L = a.depth - (empty0 ? 1 : 0);
+    BinLayout t;
+    bool s0 = false, s1 = false;
+    uint32_t S0 = 0, S1 = 0;
+    if (j < (uint32_t)a.n && in < (uint32_t)a.count) {
+        if ((s0 = bin_rx_shape(total, L, 0, a.shard_pitch, t))) S0 = t.S;
+        if ((s1 = bin_rx_shape(total, L, 1, a.shard_pitch, t))) S1 = t.S;
+    }
+    if (!s0 && !s1) {
+        if (lane == 0) {
+            a.msg_status[i] = WIRE_FALLBACK;
+            if (a.types) a.types[i] = 0;
+        }
+        return;
+    }
+    // a shard of another length than its instance's: the slot stays as it is
+    const uint32_t S = a.shard_lens ? a.shard_lens[in] : a.uniform_len;
+    const int type = (s0 && S0 == S) ? 0 : 1;
+    if (type && !(s1 && S1 == S)) {
+        if (lane == 0) {
+            a.msg_status[i] = WIRE_OTHER_LEN;
+            if (a.types) a.types[i] = (uint8_t)(s0 ? 0 : 1);
+        }
+        return;
+    }
+    const BinLayout c = bin_layout(S, L, type);
+    if (!bin_matches(m, c, type, lane)) {
+        if (lane == 0) {
+            a.msg_status[i] = WIRE_FALLBACK;
+            if (a.types) a.types[i] = (uint8_t)type;
+        }
+        return;
+    }
+    // shard and branch to slot r; the two chunks of the root are compared, not stored
+    const uint32_t rt = (total + 15u) & ~15u;
+    const uint32_t nblk = ((S + 63u) & ~63u) >> 4, nbr = 2 * L, nq = nblk + nbr + 2;
+    const size_t r = (size_t)in * a.n + j;
+    uint8_t *row = a.shards + r * a.shard_pitch;
+    uint8_t *slot = a.branches + r * (a.depth > 1 ? a.depth : 1) * 32u;
+    const uint8_t *want_root = a.roots + (size_t)in * 32;
+    uint32_t other = 0;
+    for (uint32_t q = lane; q < nq; q += 64) {
+        if (q < nblk) {
+            *reinterpret_cast<uint4 *>(row + (q << 4)) = bin_chunk16(m, rt, c.blk_off, S, q << 4);
+        } else if (q < nblk + nbr) {
+            const uint32_t o0 = (q - nblk) << 4;
+            *reinterpret_cast<uint4 *>(slot + (empty0 ? 32u : 0u) + o0) = bin_chunk16(m, rt, c.br_off, 32 * L, o0);
+        } else {
+            const uint32_t o0 = (q - nblk - nbr) << 4;
+            const uint4 v = bin_chunk16(m, rt, c.root_off, 32, o0);
+            const uint4 w = *reinterpret_cast<const uint4 *>(want_root + o0);
+            other |= (v.x ^ w.x) | (v.y ^ w.y) | (v.z ^ w.z) | (v.w ^ w.w);
+        }
+    }
+    // the zero slot of an empty level-0 sibling (or of a depth-0 tree)
+    if ((empty0 || a.depth == 0) && lane < 2) reinterpret_cast<uint4 *>(slot)[lane] = make_uint4(0, 0, 0, 0);
+    const bool wrong = __any(other != 0);
+    if (lane == 0) {
+        a.msg_status[i] = wrong ? WIRE_OTHER_ROOT : WIRE_OK;
+        if (a.types) a.types[i] = (uint8_t)type;
+        if (!wrong) a.present[r] = 1;
+    }
+}
+
 }  // namespace
 
+// The launchers choose the kernel by the payload codec (0 JSON, 1 binary).
 hipError_t rbc_launch_unmarshal_echo(const WireEchoArgs &a, hipStream_t st) {
+    if (a.codec != 0 && a.codec != 1) return hipErrorInvalidValue;
     if (a.msgs <= 0) return hipSuccess;
-    hipLaunchKernelGGL(unmarshal_echo_kernel, dim3(((unsigned)a.msgs + 3) / 4), dim3(256), 0, st, a);
+    const dim3 grid(((unsigned)a.msgs + 3) / 4), block(256);
+    if (a.codec) hipLaunchKernelGGL(unmarshal_echo_bin_kernel, grid, block, 0, st, a);
+    else hipLaunchKernelGGL(unmarshal_echo_kernel, grid, block, 0, st, a);
     return hipGetLastError();
 }
 
 hipError_t rbc_launch_unmarshal_val(const WireRxArgs &a, hipStream_t st) {
+    if (a.codec != 0 && a.codec != 1) return hipErrorInvalidValue;
     if (a.count <= 0) return hipSuccess;
-    hipLaunchKernelGGL(unmarshal_val_kernel, dim3(((unsigned)a.count + 3) / 4), dim3(256), 0, st, a);
+    const dim3 grid(((unsigned)a.count + 3) / 4), block(256);
+    if (a.codec) hipLaunchKernelGGL(unmarshal_val_bin_kernel, grid, block, 0, st, a);
+    else hipLaunchKernelGGL(unmarshal_val_kernel, grid, block, 0, st, a);
     return hipGetLastError();
 }
 
 hipError_t rbc_launch_marshal_val(const WireArgs &a, hipStream_t st) {
+    if (a.codec != 0 && a.codec != 1) return hipErrorInvalidValue;
     const uint64_t msgs = (uint64_t)a.count * a.n;
     if (!msgs) return hipSuccess;
-    hipLaunchKernelGGL(marshal_val_kernel, dim3((unsigned)((msgs + 3) / 4)), dim3(256), 0, st, a);
+    const dim3 grid((unsigned)((msgs + 3) / 4)), block(256);
+    if (a.codec) hipLaunchKernelGGL(marshal_val_bin_kernel, grid, block, 0, st, a);
+    else hipLaunchKernelGGL(marshal_val_kernel, grid, block, 0, st, a);
     return hipGetLastError();
 }
 

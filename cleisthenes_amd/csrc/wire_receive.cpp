@@ -192,6 +192,7 @@ int rbc_dev_unmarshal_echo(rbc_ctx *ctx, void *stream, int count, int msgs, cons
     a.present = present;
     a.msg_status = msg_status;
     a.types = types;
+    if (rbc_ctx_wire_codec(ctx, &a.codec) != RBC_OK) return RBC_ERR_INVALID_ARG;
     RCV_HIP(rbc_launch_unmarshal_echo(a, reinterpret_cast<hipStream_t>(stream)));
     return RBC_OK;
 }

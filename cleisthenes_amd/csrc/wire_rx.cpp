@@ -144,6 +144,7 @@ int rbc_dev_unmarshal_val(rbc_ctx *ctx, void *stream, int count, const uint8_t *
     a.roots = roots_out;
     a.types = types_out;
     a.status = status_out;
+    if (rbc_ctx_wire_codec(ctx, &a.codec) != RBC_OK) return RBC_ERR_INVALID_ARG;
     RX_HIP(rbc_launch_unmarshal_val(a, reinterpret_cast<hipStream_t>(stream)));
     return RBC_OK;
 }
@@ -225,6 +226,8 @@ int rbc_wire_validate(rbc_wire_rx *rx, int count, const uint8_t *ring, size_t ri
             if (at.type != hipMemoryTypeDevice || at.device != rx->device) return RBC_ERR_INVALID_ARG;
         }
     }
+    int codec = 0;  // the context's payload codec, read at submission
+    if (rbc_ctx_wire_codec(rx->ctx, &codec) != RBC_OK) return RBC_ERR_INVALID_ARG;
     std::lock_guard<std::mutex> lk(rx->mu);
     RX_HIP(hipSetDevice(rx->device));
     (void)rx->finish();  // the staging blocks are free again (its status stays with its ticket)
@@ -251,6 +254,7 @@ int rbc_wire_validate(rbc_wire_rx *rx, int count, const uint8_t *ring, size_t ri
     u.roots = rx->d_small + so.roots;
     u.types = rx->d_small + so.types;
     u.status = reinterpret_cast<int32_t *>(rx->d_small + so.status);
+    u.codec = codec;
     RX_HIP(rbc_launch_unmarshal_val(u, st));
     // validateMessage per decoded message (fallback messages are skipped by their status)
     ShaArgs a{};

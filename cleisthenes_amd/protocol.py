@@ -3,6 +3,8 @@
 * ``pb_encode`` / ``pb_decode``      -> pb.Message{rbc: pb.RBC{payload, type}} (pb/message.proto:11-35)
 * ``json_encode_val`` / ``..._ready`` -> Go encoding/json of ValRequest / EchoRequest / ReadyRequest
                                        (rbc/request.go:9-21)
+* ``bin_encode_val`` / ``bin_decode_val`` -> the opt-in binary VAL / ECHO payload (RBC_HAS_WIRE_BINARY);
+                                       ``payload_decode_val`` takes either form
 * ``Node``                          -> one RBC instance at one node (rbc/rbc.go:9-100: NewRBC,
                                        HandleMessage, Value, Messages)
 
@@ -17,6 +19,7 @@ from typing import List, Optional, Tuple
 
 import numpy as np
 
+from . import _lib
 from ._lib import RBC_ERR_INVALID_ARG, RBC_ERR_PROTOCOL, RBCError, check, lib
 from .rbc import Batcher, _bytes_array, _ptr
 
@@ -69,17 +72,42 @@ def json_encode_ready(root: bytes) -> bytes:
     return _emit(lib.rbc_json_encode_ready, rp, len(r))
 
 
-def json_decode_val(js: bytes) -> dict:
-    j, jp = _buf(js)
+def _decode_val(fn, name: str, payload: bytes) -> dict:
+    j, jp = _buf(payload)
     root = np.zeros(32, np.uint8)
     bl, kl = c_size_t(0), c_size_t(0)
-    rc = lib.rbc_json_decode_val(jp, len(j), _ptr(root), None, 0, byref(bl), None, 0, byref(kl))
+    rc = fn(jp, len(j), _ptr(root), None, 0, byref(bl), None, 0, byref(kl))
     if rc not in (0, RBC_ERR_INVALID_ARG):  # INVALID_ARG here: the size query
-        raise RBCError(rc, "rbc_json_decode_val")
+        raise RBCError(rc, name)
     br, blk = np.zeros(max(bl.value, 1), np.uint8), np.zeros(max(kl.value, 1), np.uint8)
-    check(lib.rbc_json_decode_val(jp, len(j), _ptr(root), _ptr(br), bl.value, byref(bl), _ptr(blk), kl.value,
-                                  byref(kl)), "rbc_json_decode_val")
+    check(fn(jp, len(j), _ptr(root), _ptr(br), bl.value, byref(bl), _ptr(blk), kl.value, byref(kl)), name)
     return {"RootHash": bytes(root), "Branch": bytes(br[:bl.value]), "Block": [bytes(blk[:kl.value])]}
+
+
+def json_decode_val(js: bytes) -> dict:
+    return _decode_val(lib.rbc_json_decode_val, "rbc_json_decode_val", js)
+
+
+def bin_encode_val(root: bytes, branch: bytes, block: bytes) -> bytes:
+    """The binary VAL / ECHO payload (include/rbc_protocol.h, version 1)."""
+    _lib.require_wire_binary()
+    r, rp = _buf(root)
+    b, bp = _buf(branch)
+    k, kp = _buf(block)
+    if lib.rbc_bin_encode_val(rp, len(r), bp, len(b), kp, len(k), None, 0) == 0:
+        raise RBCError(RBC_ERR_INVALID_ARG, "rbc_bin_encode_val")
+    return _emit(lib.rbc_bin_encode_val, rp, len(r), bp, len(b), kp, len(k))
+
+
+def bin_decode_val(payload: bytes) -> dict:
+    _lib.require_wire_binary()
+    return _decode_val(lib.rbc_bin_decode_val, "rbc_bin_decode_val", payload)
+
+
+def payload_decode_val(payload: bytes) -> dict:
+    """Either form: binary when the payload begins with 0xB1, else JSON."""
+    _lib.require_wire_binary()
+    return _decode_val(lib.rbc_payload_decode_val, "rbc_payload_decode_val", payload)
 
 
 def json_decode_ready(js: bytes) -> bytes:
@@ -109,6 +137,12 @@ class Node:
             self.close()
         except Exception:
             pass
+
+    def set_wire_codec(self, codec: str) -> None:
+        """"json" (default) or "binary": the payload of the VAL / ECHO this node
+        emits; a binary node accepts either.  Call before the first message."""
+        _lib.require_wire_binary()
+        check(lib.rbc_node_set_wire_codec(self._p, ("json", "binary").index(codec)), "rbc_node_set_wire_codec")
 
     def propose(self, value: bytes) -> None:
         v, vp = _buf(value)

@@ -302,6 +302,23 @@ class Context:
     def set_codec(self, codec: str) -> None:
         check(lib.rbc_ctx_set_codec(self._p, {"auto": 0, "matrix": 1, "fft": 2}[codec]), "rbc_ctx_set_codec")
 
+    WIRE_CODECS = ("json", "binary")
+
+    def set_wire_codec(self, codec: str) -> None:
+        """Payload codec of the wire entry points (dev_marshal_val, dev_unmarshal_val,
+        dev_unmarshal_echo, shard_commit_val, WireRx, WireReceiver): "json" (default,
+        the Go-JSON request) or "binary" (the raw form of include/rbc_protocol.h).
+        Not while a wire submission of this context is in flight."""
+        _lib.require_wire_binary()
+        check(lib.rbc_ctx_set_wire_codec(self._p, self.WIRE_CODECS.index(codec)), "rbc_ctx_set_wire_codec")
+
+    @property
+    def wire_codec(self) -> str:
+        _lib.require_wire_binary()
+        c = c_int()
+        check(lib.rbc_ctx_wire_codec(self._p, byref(c)), "rbc_ctx_wire_codec")
+        return self.WIRE_CODECS[c.value]
+
     def encode_matrix(self) -> np.ndarray:
         m = np.zeros(self.n * self.k, dtype=np.uint8)
         check(lib.rbc_ctx_encode_matrix(self._p, _ptr(m)))
@@ -467,7 +484,7 @@ class Context:
         arrs = [v if isinstance(v, np.ndarray) and v.dtype == np.uint8 and v.flags.c_contiguous
                 else _bytes_array(v) for v in values]
         Smax = max((len(a) + self.k - 1) // self.k for a in arrs)
-        need = max(lib.rbc_val_message_size(self.n, Smax, 0, 0), lib.rbc_val_message_size(self.n, Smax, self.n - 1, 0))
+        need = max(self.val_message_size(Smax, 0, 0), self.val_message_size(Smax, self.n - 1, 0))
         pitch = (need + 15) // 16 * 16
         if ring is None:
             ring = np.zeros((count, self.n, pitch), dtype=np.uint8)
@@ -747,7 +764,12 @@ class Context:
               "rbc_dev_unmarshal_echo")
 
     def val_message_size(self, shard_len: int, index: int = 0, msg_type: int = 0) -> int:
-        return lib.rbc_val_message_size(self.n, shard_len, index, msg_type)
+        """Bytes of the VAL / ECHO pb.Message in the context's wire codec."""
+        if not _lib.HAS_WIRE_BINARY:
+            return lib.rbc_val_message_size(self.n, shard_len, index, msg_type)
+        c = c_int()
+        check(lib.rbc_ctx_wire_codec(self._p, byref(c)), "rbc_ctx_wire_codec")
+        return lib.rbc_val_message_size_codec(c.value, self.n, shard_len, index, msg_type)
 
     def dev_inject_faults(self, stream, count, shards, shard_pitch, corrupt):
         check(lib.rbc_dev_inject_faults(self._p, _dv(stream), count, _dv(shards), shard_pitch, _dv(corrupt)),

@@ -249,11 +249,82 @@ int rbc_wire_receive(rbc_wire_receiver *rcv, int count, int msgs, const uint8_t 
 int rbc_wire_receive_wait(rbc_wire_receiver *rcv, uint64_t ticket);
 int rbc_wire_receive_poll(rbc_wire_receiver *rcv, uint64_t ticket, int *done);
 
+/* ---- binary VAL / ECHO payload codec (opt-in) -----------------------------
+ * Present when RBC_HAS_WIRE_BINARY is defined (the ABI version stays 7: detect
+ * the addition by symbol).  The reference pins only the pb.Message wrapper;
+ * pb.RBC.payload is opaque bytes, so a deployment whose nodes all run this
+ * library may carry the shard raw instead of as base64 inside JSON: 3/4 of
+ * the bytes on the network and across PCIe.  The wrapper is unchanged,
+ *   0x1a varint(R) 0x0a varint(J) <payload, J bytes> [0x10 type]
+ * with R = 1 + varint_len(J) + J + (type ? 2 : 0), and the payload of VAL /
+ * ECHO is (version 1):
+ *   offset      size   field
+ *   0           1      0xB1 magic (no JSON text begins with it, so each
+ *                      decoder rejects the other's payload)
+ *   1           1      0x01 version
+ *   2           1      L: number of 32-byte branch entries, Go flat form
+ *   3           1      0x00 reserved, must be zero
+ *   4           4      S: shard length, little-endian u32
+ *   8           32     root
+ *   40          32*L   branch
+ *   40 + 32*L   S      shard
+ * J = 40 + 32*L + S, nothing behind the shard.  READY keeps its JSON payload.
+ * Every (root, branch, shard, type) has exactly one encoding; a message's
+ * length alone does not fix its type ((S, VAL) and (S - 2, ECHO) mostly share
+ * a total), and some totals cannot occur (a varint grows there).
+ *
+ * rbc_bin_encode_val: root_len must be 32 and branch_len a multiple of 32
+ * (at most 255 entries), else 0 is returned; block_len 0 is allowed (S = 0,
+ * as "Block":null).  Returns the size; writes only when it fits.
+ * rbc_bin_decode_val: RBC_ERR_PROTOCOL unless len >= 40, magic, version and
+ * reserved byte are right and len == 40 + 32*L + S exactly;
+ * RBC_ERR_INVALID_ARG (lens set) when a buffer is short.
+ * rbc_payload_decode_val dispatches on the first payload byte: 0xB1 to the
+ * binary decoder, anything else to rbc_json_decode_val -- the one call a
+ * shim's fallback path needs. */
+#define RBC_HAS_WIRE_BINARY 1
+#define RBC_WIRE_CODEC_JSON 0
+#define RBC_WIRE_CODEC_BINARY 1
+#define RBC_BIN_MAGIC 0xB1
+#define RBC_BIN_VERSION 0x01
+size_t rbc_bin_encode_val(const uint8_t *root, size_t root_len, const uint8_t *branch, size_t branch_len,
+                          const uint8_t *block, size_t block_len, uint8_t *out, size_t cap);
+int rbc_bin_decode_val(const uint8_t *payload, size_t len, uint8_t *root_out, uint8_t *branch_out, size_t branch_cap,
+                       size_t *branch_len, uint8_t *block_out, size_t block_cap, size_t *block_len);
+int rbc_payload_decode_val(const uint8_t *payload, size_t len, uint8_t *root_out, uint8_t *branch_out,
+                           size_t branch_cap, size_t *branch_len, uint8_t *block_out, size_t block_cap,
+                           size_t *block_len);
+/* rbc_val_message_size for a codec (codec 0 equals it); 0 for an unknown codec. */
+size_t rbc_val_message_size_codec(int codec, int n, uint32_t shard_len, uint32_t index, int type);
+/* The codec of a context's wire entry points, RBC_WIRE_CODEC_JSON by default.
+ * rbc_dev_marshal_val, rbc_dev_unmarshal_val, rbc_dev_unmarshal_echo,
+ * rbc_shard_commit_val, rbc_wire_validate and rbc_wire_receive read it when
+ * they submit; their signatures and their JSON behaviour are unchanged.  In
+ * binary mode "canonical" means: rbc_pb_decode_rbc + rbc_bin_decode_val accept
+ * the message, the wrapper is minimal (minimal varints, exactly these fields
+ * in this order), L is the flat branch length of leaf idx in an n-leaf tree
+ * and 1 <= S <= the row pitch; a JSON message is RBC_WIRE_FALLBACK there, and
+ * a binary one is in JSON mode.  A binary message's length leaves up to two
+ * shapes, one per type ((S, VAL) and (S - 2, ECHO)): rbc_dev_unmarshal_val
+ * keeps the one whose header the message carries; rbc_dev_unmarshal_echo takes
+ * the one of the instance's shard length (none: RBC_WIRE_OTHER_LEN) and checks
+ * the message against that one alone.  Every node of a deployment emits one codec.
+ * Changing the codec while a wire submission of the context is in flight is
+ * the caller's error. */
+int rbc_ctx_set_wire_codec(rbc_ctx *ctx, int codec);
+int rbc_ctx_wire_codec(const rbc_ctx *ctx, int *codec);
+
 /* ---- RBC instance (one proposer's broadcast, seen at one node) ----------- */
 typedef struct rbc_node rbc_node;
 /* NewRBC (rbc/rbc.go:38). */
 int rbc_node_create(rbc_batcher *batcher, int n, int f, int self, int proposer, rbc_node **out);
 void rbc_node_destroy(rbc_node *node); /* waits for its outstanding GPU work */
+/* The payload codec of the VAL / ECHO this node emits (RBC_HAS_WIRE_BINARY),
+ * RBC_WIRE_CODEC_JSON by default; call it before the first message.  A JSON
+ * node behaves as ever (a binary VAL / ECHO is malformed to it); a binary node
+ * emits binary VAL / ECHO and accepts either form (rbc_payload_decode_val's
+ * rule), so a rolling upgrade works.  READY is JSON in both. */
+int rbc_node_set_wire_codec(rbc_node *node, int codec);
 /* Proposer only: shard + commit `value` (copied), then VAL(h, b_j, s_j) to every j.
  * The broadcast payload is framed as [u64 little-endian len][value] (len 0 is
  * allowed), so rbc_node_value returns exactly these bytes. */

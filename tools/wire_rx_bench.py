@@ -24,8 +24,17 @@ be identical (a digest of them is compared), and so must C's and R's statuses
 and value bytes.  About 1 % of the messages carry one corrupted shard
 character, so both verdict values occur.
 
+--codec json|binary (or both, comma-separated) chooses the payload codec the
+epoch is encoded in and the context decodes (include/rbc_protocol.h,
+RBC_HAS_WIRE_BINARY).  With both, every leg runs once per codec in the same
+invocation, json first, on the same shards with the same messages corrupted;
+the verdict and result digests must be identical across the codecs, and each
+leg's binary run is called a win or a loss against its json run only where
+their min-max ranges do not overlap.  Leg A is the JSON host decoder's.
+
   python tools/wire_rx_bench.py --legs A,B,K --out profiles/wire_rx/c2.json
   python tools/wire_rx_bench.py --legs C,R --out profiles/wire_rx/c2_receive.json
+  python tools/wire_rx_bench.py --legs B,R,K --codec json,binary --out profiles/wire_rx/c2_binary.json
 """
 import argparse
 import ctypes
@@ -85,18 +94,23 @@ def build_epoch(ca, ctx, a):
         senders = np.sort(rng.permutation(n)[:a.echoes])
         idx[i * a.echoes:(i + 1) * a.echoes] = senders
         r2[i * a.echoes:(i + 1) * a.echoes] = msgs[(i % distinct) * n + senders, :slot]
-    # ~1 % corrupted: one shard character replaced by another of the alphabet
-    blk0 = mlen - 5 - (S + 2) // 3 * 4  # '"]}' + the ECHO type field behind the block
+    # ~1 % corrupted: one shard character replaced by another of the alphabet (binary: the first
+    # shard byte that character encodes, one bit flipped): the same messages under either codec
+    binary = a.codec == "binary"
+    blk0 = mlen - 2 - S if binary else mlen - 5 - (S + 2) // 3 * 4  # the ECHO type field (and '"]}') behind the block
     for m in rng.permutation(count)[:max(count // 100, 1)]:
-        at = blk0 + int(rng.integers(0, S // 3 * 4))
-        r2[m, at] = ord("A") if r2[m, at] != ord("A") else ord("B")
+        ch = int(rng.integers(0, S // 3 * 4))
+        if binary:
+            r2[m, blk0 + ch * 3 // 4] ^= 1
+        else:
+            r2[m, blk0 + ch] = ord("A") if r2[m, blk0 + ch] != ord("A") else ord("B")
     offs = np.arange(count, dtype=np.uint64) * slot
     lens = np.full(count, mlen, np.uint32)
     inst = np.repeat(np.arange(a.instances, dtype=np.uint32), a.echoes)
     roots = np.ascontiguousarray(c["roots"])[np.arange(a.instances) % distinct]
     return {"ring": ring, "offs": offs, "lens": lens, "idx": idx, "count": count, "S": S, "mlen": mlen,
             "inst": inst, "roots": np.ascontiguousarray(roots), "instances": a.instances,
-            "wire_bytes": int(count) * mlen, "shard_bytes": int(count) * S}
+            "wire_bytes": int(count) * mlen, "shard_bytes": int(count) * S, "ring_bytes": int(ring.nbytes)}
 
 
 def timed(fn, warmup, epochs):
@@ -122,6 +136,7 @@ def digest(v):
 
 def leg_a(ca, ctx, e, a):
     import numpy as np
+    assert a.codec == "json", "leg A is the JSON host decoder's path"
     so = os.path.join(ROOT, "tools", "libwire_rx_decode.so")
     if not os.path.exists(so):
         subprocess.run(["make", "-C", os.path.join(ROOT, "tools"), "libwire_rx_decode.so"], check=True)
@@ -281,11 +296,61 @@ def leg_r(ca, ctx, e, a):
 def child(a):
     import cleisthenes_amd as ca
     ctx = ca.Context(a.n, a.f)
+    if a.codec != "json":  # before the epoch is built: the marshal kernel writes the codec's messages
+        ctx.set_wire_codec(a.codec)
     e = build_epoch(ca, ctx, a)
     r = {"A": leg_a, "B": leg_b, "K": leg_k, "C": leg_c, "R": leg_r}[a.leg](ca, ctx, e, a)
     r.update(leg=a.leg, count=e["count"], shard_len=e["S"], message_len=e["mlen"], wire_bytes=e["wire_bytes"],
-             shard_bytes=e["shard_bytes"], library=os.path.relpath(ca.rbc.library_path(), ROOT))
+             shard_bytes=e["shard_bytes"], ring_bytes=e["ring_bytes"], codec=a.codec, library=os.path.relpath(ca.rbc.library_path(), ROOT))
     print("WIRE_RX_LEG " + json.dumps(r), flush=True)
+
+
+def run_leg(a, leg, codec):
+    """One leg in a child process of its own, under its own time limit."""
+    cmd = [sys.executable, os.path.abspath(__file__), "--leg", leg, "--codec", codec] + \
+        [x for k in ("n", "f", "instances", "echoes", "shard_len", "distinct", "warmup", "epochs", "seed")
+         for x in ("--" + k.replace("_", "-"), str(getattr(a, k)))]
+    env = dict(os.environ, OMP_NUM_THREADS=os.environ.get("OMP_NUM_THREADS", str(THREADS)))
+    try:
+        r = subprocess.run(cmd, capture_output=True, text=True, timeout=a.leg_timeout, env=env)
+    except subprocess.TimeoutExpired:
+        sys.exit(f"leg {leg} ({codec}): no result within {a.leg_timeout} s; stopping")
+    line = [x for x in r.stdout.splitlines() if x.startswith("WIRE_RX_LEG ")]
+    if r.returncode != 0 or not line:
+        sys.stderr.write(r.stdout[-2000:] + r.stderr[-4000:])
+        sys.exit(f"leg {leg} ({codec}) failed (exit {r.returncode}); stopping")
+    res = json.loads(line[-1][len("WIRE_RX_LEG "):])
+    print(f"leg {leg} ({codec}): median {res['median_s'] * 1e3:.3f} ms", file=sys.stderr, flush=True)
+    return res
+
+
+def both_codecs(a, want, codecs):
+    """Every leg once per codec, the codecs alternating; binary against json by min-max range."""
+    res = {"bench": "wire_rx", "geometry": {"n": a.n, "f": a.f, "instances": a.instances, "echoes": a.echoes,
+                                            "shard_len": a.shard_len}, "threads": THREADS, "warmup": a.warmup,
+           "epochs": a.epochs, "codecs": codecs}
+    same = True
+    for leg in want:
+        runs = {c: run_leg(a, leg, c) for c in codecs}
+        j, b = runs["json"], runs["binary"]
+        cmp = {"binary_over_json_median": j["median_s"] / b["median_s"],
+               "binary_vs_json": "win" if b["max_s"] < j["min_s"] else "loss" if b["min_s"] > j["max_s"] else "tie",
+               "ring_bytes_binary_over_json": b["ring_bytes"] / j["ring_bytes"]}
+        for key in ("verdict_sha256", "result_sha256"):
+            if key in j:
+                cmp[key + "_identical"] = j[key] == b[key]
+                same = same and cmp[key + "_identical"]
+        res[NAMES[leg] + "[binary vs json]"] = cmp
+        for c in codecs:
+            res[f"{NAMES[leg]}[{c}]"] = runs[c]
+    text = json.dumps(res, indent=1)
+    if a.out:
+        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+        with open(a.out, "w") as fh:
+            fh.write(text + "\n")
+    print(text)
+    if not same:
+        sys.exit("the two codecs gave different verdicts or results")
 
 
 def main():
@@ -302,33 +367,29 @@ def main():
     p.add_argument("--leg-timeout", type=int, default=240, help="seconds per leg")
     p.add_argument("--out", default=None)
     p.add_argument("--legs", default="A,B,K", help="comma-separated legs to run, of A B K C R")
+    p.add_argument("--codec", default="json", help="payload codec: json, binary, or json,binary for both")
     p.add_argument("--leg", choices=list(NAMES), default=None, help=argparse.SUPPRESS)
     a = p.parse_args()
     if a.warmup < 2 or a.epochs < 5:
         p.error("at least 2 warm-up and 5 timed epochs")
+    codecs = [x for x in a.codec.split(",") if x]
+    if not codecs or any(x not in ("json", "binary") for x in codecs) or len(set(codecs)) != len(codecs):
+        p.error("--codec takes json, binary or json,binary")
     if a.leg:
         return child(a)
     want = [x for x in a.legs.split(",") if x]
     if not want or any(x not in NAMES for x in want):
         p.error("--legs takes a comma-separated list of " + " ".join(NAMES))
-    legs = {}
-    for leg in want:
-        cmd = [sys.executable, os.path.abspath(__file__), "--leg", leg] + \
-            [x for k in ("n", "f", "instances", "echoes", "shard_len", "distinct", "warmup", "epochs", "seed")
-             for x in ("--" + k.replace("_", "-"), str(getattr(a, k)))]
-        env = dict(os.environ, OMP_NUM_THREADS=os.environ.get("OMP_NUM_THREADS", str(THREADS)))
-        try:
-            r = subprocess.run(cmd, capture_output=True, text=True, timeout=a.leg_timeout, env=env)
-        except subprocess.TimeoutExpired:
-            sys.exit(f"leg {leg}: no result within {a.leg_timeout} s; stopping")
-        line = [x for x in r.stdout.splitlines() if x.startswith("WIRE_RX_LEG ")]
-        if r.returncode != 0 or not line:
-            sys.stderr.write(r.stdout[-2000:] + r.stderr[-4000:])
-            sys.exit(f"leg {leg} failed (exit {r.returncode}); stopping")
-        legs[leg] = json.loads(line[-1][len("WIRE_RX_LEG "):])
+    if "A" in want and codecs != ["json"]:
+        p.error("leg A is the JSON host decoder's path: run it with --codec json")
+    if len(codecs) == 2:
+        return both_codecs(a, want, codecs)
+    legs = {leg: run_leg(a, leg, codecs[0]) for leg in want}
     res = {"bench": "wire_rx", "geometry": {"n": a.n, "f": a.f, "instances": a.instances, "echoes": a.echoes,
                                             "shard_len": a.shard_len}, "threads": THREADS, "warmup": a.warmup,
            "epochs": a.epochs}
+    if codecs != ["json"]:
+        res["codec"] = codecs[0]
     same = True
     if "A" in legs and "B" in legs:
         same = legs["A"]["verdict_sha256"] == legs["B"]["verdict_sha256"]
