@@ -15,6 +15,7 @@ from .rbc import (  # noqa: F401
     RBCError,
     Stream,
     Event,
+    WireQuorum,
     WireReceiver,
     WireRx,
     device_count,
@@ -22,5 +23,5 @@ from .rbc import (  # noqa: F401
     split_rows,
 )
 
-__all__ = ["Batcher", "Context", "DeviceBuffer", "Encoder", "RBCError", "Stream", "Event", "WireReceiver", "WireRx",
-           "device_count", "pinned_empty", "split_rows"]
+__all__ = ["Batcher", "Context", "DeviceBuffer", "Encoder", "RBCError", "Stream", "Event", "WireQuorum",
+           "WireReceiver", "WireRx", "device_count", "pinned_empty", "split_rows"]

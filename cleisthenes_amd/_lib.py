@@ -210,6 +210,18 @@ _SIGS = {
     "rbc_ctx_set_wire_codec": (c_int, [c_void_p, c_int]),
     "rbc_ctx_wire_codec": (c_int, [c_void_p, POINTER(c_int)]),
     "rbc_node_set_wire_codec": (c_int, [c_void_p, c_int]),
+    # READYs from wire bytes and the quorum tally (RBC_HAS_WIRE_READY)
+    "rbc_dev_unmarshal_ready": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p,
+                                        c_void_p, c_void_p, c_void_p, c_void_p]),
+    "rbc_dev_quorum": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p,
+                               c_void_p]),
+    "rbc_wire_quorum_create": (c_int, [c_void_p, c_int, c_int, c_size_t, POINTER(c_void_p)]),
+    "rbc_wire_quorum_destroy": (None, [c_void_p]),
+    "rbc_wire_quorum": (c_int, [c_void_p, c_int, c_int, c_void_p, c_size_t, c_void_p, c_void_p, c_void_p, c_void_p,
+                                c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                POINTER(c_uint64)]),
+    "rbc_wire_quorum_wait": (c_int, [c_void_p, c_uint64]),
+    "rbc_wire_quorum_poll": (c_int, [c_void_p, c_uint64, POINTER(c_int)]),
     # parity-only shard commit (RBC_HAS_SHARD_COMMIT_PARITY)
     "rbc_dev_shard_commit_parity": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_uint64, c_void_p, c_uint32,
                                             c_void_p, c_void_p, c_uint32, c_void_p, c_void_p, c_void_p, c_void_p]),
@@ -229,7 +241,7 @@ _SIGS = {
 }
 
 # Additions made at an unchanged ABI version are detected by symbol, as their
-# header macros say (RBC_HAS_WIRE_RX, RBC_HAS_WIRE_RECEIVE, RBC_HAS_WIRE_BINARY): another build of
+# header macros say (RBC_HAS_WIRE_RX, RBC_HAS_WIRE_RECEIVE, RBC_HAS_WIRE_BINARY, RBC_HAS_WIRE_READY): another build of
 # ABI 7 (RBC_GPU_LIB) may lack them.  They are then left unbound, and using one
 # raises.
 _BY_SYMBOL = ("rbc_dev_unmarshal_val", "rbc_wire_rx_create", "rbc_wire_rx_destroy", "rbc_wire_validate",
@@ -239,13 +251,17 @@ _BY_SYMBOL_RECEIVE = ("rbc_dev_unmarshal_echo", "rbc_wire_receiver_create", "rbc
 _BY_SYMBOL_BINARY = ("rbc_bin_encode_val", "rbc_bin_decode_val", "rbc_payload_decode_val",
                      "rbc_val_message_size_codec", "rbc_ctx_set_wire_codec", "rbc_ctx_wire_codec",
                      "rbc_node_set_wire_codec")
+_BY_SYMBOL_READY = ("rbc_dev_unmarshal_ready", "rbc_dev_quorum", "rbc_wire_quorum_create", "rbc_wire_quorum_destroy",
+                    "rbc_wire_quorum", "rbc_wire_quorum_wait", "rbc_wire_quorum_poll")
 HAS_WIRE_RX = all(hasattr(lib, _name) for _name in _BY_SYMBOL)
 HAS_WIRE_RECEIVE = all(hasattr(lib, _name) for _name in _BY_SYMBOL_RECEIVE)
 HAS_WIRE_BINARY = all(hasattr(lib, _name) for _name in _BY_SYMBOL_BINARY)
+HAS_WIRE_READY = all(hasattr(lib, _name) for _name in _BY_SYMBOL_READY)
 
 for _name, (_res, _args) in _SIGS.items():
     if ((_name in _BY_SYMBOL and not HAS_WIRE_RX) or (_name in _BY_SYMBOL_RECEIVE and not HAS_WIRE_RECEIVE)
-            or (_name in _BY_SYMBOL_BINARY and not HAS_WIRE_BINARY)):
+            or (_name in _BY_SYMBOL_BINARY and not HAS_WIRE_BINARY)
+            or (_name in _BY_SYMBOL_READY and not HAS_WIRE_READY)):
         continue
     _fn = getattr(lib, _name)
     _fn.restype = _res
@@ -266,6 +282,11 @@ def require_wire_binary() -> None:
     if not HAS_WIRE_BINARY:
         raise ImportError(f"{LIB_PATH} has no binary payload codec (RBC_HAS_WIRE_BINARY): "
                           "rbc_ctx_set_wire_codec missing")
+
+
+def require_wire_ready() -> None:
+    if not HAS_WIRE_READY:
+        raise ImportError(f"{LIB_PATH} has no READY path (RBC_HAS_WIRE_READY): rbc_wire_quorum missing")
 
 
 def header_functions(path: str = None):
@@ -306,6 +327,8 @@ RBC_WIRE_OK, RBC_WIRE_FALLBACK = 0, 1
 RBC_WIRE_OTHER_ROOT, RBC_WIRE_OTHER_LEN = 2, 3
 # payload codec of the wire path (RBC_HAS_WIRE_BINARY)
 RBC_WIRE_CODEC_JSON, RBC_WIRE_CODEC_BINARY = 0, 1
+# flags of rbc_dev_quorum / rbc_wire_quorum (RBC_HAS_WIRE_READY)
+RBC_QUORUM_ECHO, RBC_QUORUM_AMPLIFY, RBC_QUORUM_SEND_READY, RBC_QUORUM_DELIVER = 1, 2, 4, 8
 
 
 class RBCError(Exception):

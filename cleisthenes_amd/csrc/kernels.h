@@ -291,6 +291,51 @@ struct WireEchoArgs {
 };
 hipError_t rbc_launch_unmarshal_echo(const WireEchoArgs &a, hipStream_t st);
 
+// READY unmarshaling (wire.hip, unmarshal_ready_kernel): message m, read like
+// WireEchoArgs' message m, is a READY of the member at leaf idx[m] for
+// instance inst[m].  READY has one canonical form of one length under both
+// payload codecs: rbc_pb_encode_rbc(RBC_MSG_READY, rbc_json_encode_ready(root, 32)).
+// Status in this order: lens[m] != msg_len, inst[m] >= count or idx[m] >= n
+// (decided before any byte of the message is read) -> WIRE_FALLBACK; a byte
+// not canonical -> WIRE_FALLBACK; the root (decoded in registers, never stored)
+// != roots[inst[m]] -> WIRE_OTHER_ROOT; else WIRE_OK and
+// ready[inst[m]*n + idx[m]] = 1.  A message writes msg_status[m] and that one
+// byte only; the kernel never clears a byte of ready, so two messages naming
+// one slot store the same 1.
+struct WireReadyArgs {
+    int count, msgs, n;        // instances, messages, members
+    uint32_t msg_len;          // the host encoder's READY size; the launcher rejects any other than the kernel's
+    const uint8_t *ring;
+    const uint64_t *offs;      // [msgs] % 16 == 0
+    const uint32_t *lens;      // [msgs]
+    const uint32_t *inst;      // [msgs] < count
+    const uint8_t *idx;        // [msgs] sender's leaf index
+    const uint8_t *roots;      // [count][32] the root each instance collects READYs for
+    uint8_t *ready;            // [count][n]: 1 written for WIRE_OK, else untouched
+    int32_t *msg_status;       // [msgs]
+};
+hipError_t rbc_launch_unmarshal_ready(const WireReadyArgs &a, hipStream_t st);
+
+// Per-instance quorum tally (wire.hip, quorum_kernel): E = non-zero bytes of
+// valid[i][0..n) (valid NULL: 0), R = non-zero bytes of ready[i][0..n), st =
+// status[i] (status NULL: nothing is known, `have` is false).
+//   have       = st == 0 && (E >= n-f || (R >= 2f+1 && E >= n-2f))
+//   send_ready = R >= f+1 || have
+//   if send_ready && self >= 0 && !ready[i][self]: ready[i][self] = 1, R += 1
+//   deliver    = st == 0 && R >= 2f+1 && E >= n-2f
+// flags[i]: 1 E >= n-f, 2 R >= f+1 before the own bit, 4 send_ready, 8 deliver.
+struct QuorumArgs {
+    int count, n, f, self;     // self in [-1, n): -1 turns the own-READY write off
+    const uint8_t *valid;      // [count][n], nullable
+    uint8_t *ready;            // [count][n]; only ready[i][self] is ever written
+    const int32_t *status;     // [count], nullable
+    uint32_t *echo_counts;     // [count] E
+    uint32_t *ready_counts;    // [count] R after the own bit
+    uint8_t *flags;            // [count]
+};
+enum { QUORUM_ECHO = 1, QUORUM_AMPLIFY = 2, QUORUM_SEND_READY = 4, QUORUM_DELIVER = 8 };
+hipError_t rbc_launch_quorum(const QuorumArgs &a, hipStream_t st);
+
 hipError_t rbc_launch_rs_fft(const FftArgs &a, hipStream_t st);
 
 int rbc_gf_pick_rc(int R, int rcmax);  // GfArgs::rc; the rule is host_shared.h's rbc_gf_pick_rc_impl

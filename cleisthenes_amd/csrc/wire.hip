@@ -23,6 +23,9 @@
 // else left to the host decoder.  unmarshal_echo_kernel is the same decode
 // for a receiver that batches an epoch's ECHOs: it writes each shard and
 // branch once, at the leaf position of its instance's shard set.
+// unmarshal_ready_kernel decodes the third kind, READY, into a per-instance
+// sender bitmap, and quorum_kernel turns that bitmap and verify's valid[] into
+// the protocol's counts and decisions.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -529,6 +532,121 @@ __global__ __launch_bounds__(256) void unmarshal_echo_kernel(WireEchoArgs a) {
 }
 
 // ---------------------------------------------------------------------------
+// READY (include/rbc_protocol.h, RBC_HAS_WIRE_READY).  The third message kind
+// has one canonical form of one length under both payload codecs,
+//   0x1a R 0x0a J {"RootHash":"<44 characters>"} 0x10 0x02
+// so there is no shape to derive: a message of another length is
+// WIRE_FALLBACK before a byte of it is read, and every offset below is a
+// constant.  The 44 characters are the base64 of 32 bytes: ten full groups and
+// one padded by a single '=', which unb64_chunk_slow demands at the last
+// character and refuses at the one before it -- the 31- and 33-byte roots,
+// which encode to 44 characters too, fall back there.
+//
+// A message is 65 bytes, five 16-byte chunks, and has four pieces of work of
+// at most 16 bytes each: the two halves of the root (the first wholly inside
+// full groups: unb64_chunk16; the second holds the padded group:
+// unb64_chunk_slow), the 17 literal bytes in front of the root and the 4
+// behind it.  One lane takes each, so a message is a group of 4 lanes, a wave
+// holds 16 messages and a block 64; a group never straddles a wave, and its
+// verdict is one nibble of the wave's ballot.  No LDS, no cross-lane data.
+// ---------------------------------------------------------------------------
+constexpr uint32_t kReadyJ = 13 + 44 + 2;          // '{"RootHash":"', the root's base64, '"}'
+constexpr uint32_t kReadyR = 1 + 1 + kReadyJ + 2;  // 0x0a varint(J), the payload, 0x10 type
+constexpr uint32_t kReadyTotal = 1 + 1 + kReadyR;  // 0x1a varint(R), the rest
+constexpr uint32_t kReadyRoot = 4 + 13;            // where the root's base64 begins
+constexpr uint32_t kReadyTail = kReadyRoot + 44;   // '"}' and the type field
+static_assert(kReadyJ < 128 && kReadyR < 128, "both varints are one byte");
+static_assert(kReadyTail + 4 == kReadyTotal, "the READY layout");
+
+// byte p of every canonical READY, for p outside the root's base64
+__device__ __forceinline__ uint32_t ready_byte(uint32_t p) {
+    if (p < 4) return p == 0 ? 0x1au : p == 1 ? kReadyR : p == 2 ? 0x0au : kReadyJ;
+    if (p < kReadyRoot) return (uint8_t)kLit[p - 4];
+    const uint32_t t = p - kReadyTail;
+    return t == 0 ? '"' : t == 1 ? '}' : t == 2 ? 0x10u : 0x02u;
+}
+
+// four lanes per message; 16 messages per wave, 64 per block
+__global__ __launch_bounds__(256) void unmarshal_ready_kernel(WireReadyArgs a) {
+    const uint32_t m = blockIdx.x * 64 + (threadIdx.x >> 2);
+    const uint32_t lane = threadIdx.x & 63, part = lane & 3;
+    const bool live = m < (uint32_t)a.msgs;
+    // length, instance and leaf: all that is decided before a byte of the message is read
+    uint32_t in = 0, j = 0;
+    bool shaped = false;
+    if (live) {
+        in = a.inst[m];
+        j = a.idx[m];
+        shaped = a.lens[m] == kReadyTotal && in < (uint32_t)a.count && j < (uint32_t)a.n;
+    }
+    uint32_t bad = 0, other = 0;
+    if (shaped) {
+        const uint8_t *msg = a.ring + a.offs[m];
+        if (part < 2) {
+            // half a root, compared with the instance's and not stored
+            const uint32_t o0 = part << 4;
+            uint4 v;
+            if (4 * (o0 / 3) + 24 <= 32 / 3 * 4) v = unb64_chunk16(msg, kReadyRoot, o0, bad);
+            else v = unb64_chunk_slow(msg, kReadyRoot, 32, o0, bad);
+            const uint4 w = *reinterpret_cast<const uint4 *>(a.roots + (size_t)in * 32 + o0);
+            other = (v.x ^ w.x) | (v.y ^ w.y) | (v.z ^ w.z) | (v.w ^ w.w);
+        } else {
+            // the header and the JSON literal in front of the root, or '"}' and the type field behind it
+            const uint32_t p0 = part == 2 ? 0u : kReadyTail, p1 = part == 2 ? kReadyRoot : kReadyTotal;
+            for (uint32_t p = p0; p < p1; ++p)
+                if (msg[p] != ready_byte(p)) bad = 1;
+        }
+    }
+    // every lane of the wave is here: the group's verdict is its nibble of the ballots
+    const uint32_t sh = lane & ~3u;
+    const uint32_t fail = (uint32_t)(__ballot(bad != 0) >> sh) & 0xfu;
+    const uint32_t wrong = (uint32_t)(__ballot(other != 0) >> sh) & 0xfu;
+    if (live && part == 0) {
+        const int st = (!shaped || fail) ? WIRE_FALLBACK : wrong ? WIRE_OTHER_ROOT : WIRE_OK;
+        a.msg_status[m] = st;
+        if (st == WIRE_OK) a.ready[(size_t)in * a.n + j] = 1;
+    }
+}
+
+// quorum_kernel: the thresholds of rbc_node's advance() over counts
+// (kernels.h, QuorumArgs).  One wave per instance; 4 waves (instances) per
+// block.  n reaches 256, so the two counts take up to four wave-wide steps of
+// one ballot and one popcount each; lane 0 then applies the rules.  Only
+// ready[i][self] is ever written, by the wave that counted it.
+__global__ __launch_bounds__(256) void quorum_kernel(QuorumArgs a) {
+    const uint32_t i = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (i >= (uint32_t)a.count) return;  // wave-uniform
+    const uint32_t lane = threadIdx.x & 63, n = (uint32_t)a.n;
+    const uint8_t *valid = a.valid ? a.valid + (size_t)i * n : nullptr;
+    uint8_t *ready = a.ready + (size_t)i * n;
+    uint32_t E = 0, R = 0;
+    for (uint32_t t0 = 0; t0 < n; t0 += 64) {  // a wave-uniform trip count: every lane reaches the ballots
+        const uint32_t t = t0 + lane;
+        const bool inside = t < n;
+        E += (uint32_t)__popcll(__ballot(inside && valid && valid[t] != 0));
+        R += (uint32_t)__popcll(__ballot(inside && ready[t] != 0));
+    }
+    if (lane) return;
+    const int32_t st = a.status ? a.status[i] : 1;  // no status: nothing is known about the interpolation
+    const uint32_t f = (uint32_t)a.f;
+    // n - f and n - 2f as signed numbers: a geometry with 2f > n has no quorum, not a wrapped one
+    const bool echo_q = (int64_t)E >= (int64_t)n - (int64_t)f;
+    const bool echo_k = (int64_t)E >= (int64_t)n - 2 * (int64_t)f;
+    const bool amplify = R >= f + 1;
+    const bool have = st == 0 && (echo_q || (R >= 2 * f + 1 && echo_k));
+    const bool send_ready = amplify || have;
+    if (send_ready && a.self >= 0 && !ready[a.self]) {  // the node's own READY counts
+        ready[a.self] = 1;
+        ++R;
+    }
+    const bool deliver = st == 0 && R >= 2 * f + 1 && echo_k;
+    a.echo_counts[i] = E;
+    a.ready_counts[i] = R;
+    a.flags[i] = (uint8_t)((echo_q ? QUORUM_ECHO : 0) | (amplify ? QUORUM_AMPLIFY : 0) |
+                           (send_ready ? QUORUM_SEND_READY : 0) | (deliver ? QUORUM_DELIVER : 0));
+}
+
+// ---------------------------------------------------------------------------
 // The binary payload codec (include/rbc_protocol.h, RBC_HAS_WIRE_BINARY): the
 // same pb.Message wrapper around
 //   0xB1 0x01 L 0x00 | S as u32 LE | root[32] | branch[32*L] | shard[S]
@@ -841,6 +959,24 @@ hipError_t rbc_launch_unmarshal_echo(const WireEchoArgs &a, hipStream_t st) {
     const dim3 grid(((unsigned)a.msgs + 3) / 4), block(256);
     if (a.codec) hipLaunchKernelGGL(unmarshal_echo_bin_kernel, grid, block, 0, st, a);
     else hipLaunchKernelGGL(unmarshal_echo_kernel, grid, block, 0, st, a);
+    return hipGetLastError();
+}
+
+// READY has one form under both codecs.  msg_len is what the host encoder
+// emits for a 32-byte root: a kernel built for another layout refuses to run.
+hipError_t rbc_launch_unmarshal_ready(const WireReadyArgs &a, hipStream_t st) {
+    if (a.msg_len != kReadyTotal || a.n < 1 || a.n > 256) return hipErrorInvalidValue;
+    if (a.msgs <= 0) return hipSuccess;
+    const dim3 grid(((unsigned)a.msgs + 63) / 64), block(256);
+    hipLaunchKernelGGL(unmarshal_ready_kernel, grid, block, 0, st, a);
+    return hipGetLastError();
+}
+
+hipError_t rbc_launch_quorum(const QuorumArgs &a, hipStream_t st) {
+    if (a.n < 1 || a.f < 0 || a.self < -1 || a.self >= a.n) return hipErrorInvalidValue;
+    if (a.count <= 0) return hipSuccess;
+    const dim3 grid(((unsigned)a.count + 3) / 4), block(256);
+    hipLaunchKernelGGL(quorum_kernel, grid, block, 0, st, a);
     return hipGetLastError();
 }
 

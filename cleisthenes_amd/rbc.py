@@ -21,7 +21,7 @@ import numpy as np
 from . import _lib
 from ._lib import RBCError, check, lib
 
-__all__ = ["Context", "Encoder", "DeviceBuffer", "Stream", "Event", "RBCError", "device_count"]
+__all__ = ["Context", "Encoder", "DeviceBuffer", "Stream", "Event", "RBCError", "WireQuorum", "device_count"]
 
 
 def device_count() -> int:
@@ -763,6 +763,23 @@ class Context:
                                          _dv(branches), _dv(present), _dv(msg_status), _dv(types)),
               "rbc_dev_unmarshal_echo")
 
+    def dev_unmarshal_ready(self, stream, count, msgs, ring, offs, lens, inst, idx, roots, ready, msg_status):
+        """Received READY pb.Message bytes decoded into the [count][n] sender
+        bitmap `ready` (include/rbc_protocol.h): msg_status 0 = ready[inst][idx]
+        set, 1 = not canonical, 2 = another root than its instance's."""
+        _lib.require_wire_ready()
+        check(lib.rbc_dev_unmarshal_ready(self._p, _dv(stream), count, msgs, _dv(ring), _dv(offs), _dv(lens),
+                                          _dv(inst), _dv(idx), _dv(roots), _dv(ready), _dv(msg_status)),
+              "rbc_dev_unmarshal_ready")
+
+    def dev_quorum(self, stream, count, valid, ready, status, self_id, echo_counts, ready_counts, flags):
+        """Per-instance ECHO / READY counts and the RBC_QUORUM_* decisions of
+        node self_id (-1: none) over valid [count][n] (or None), ready
+        [count][n] and status [count] (or None)."""
+        _lib.require_wire_ready()
+        check(lib.rbc_dev_quorum(self._p, _dv(stream), count, _dv(valid), _dv(ready), _dv(status), self_id,
+                                 _dv(echo_counts), _dv(ready_counts), _dv(flags)), "rbc_dev_quorum")
+
     def val_message_size(self, shard_len: int, index: int = 0, msg_type: int = 0) -> int:
         """Bytes of the VAL / ECHO pb.Message in the context's wire codec."""
         if not _lib.HAS_WIRE_BINARY:
@@ -945,6 +962,89 @@ class WireReceiver:
                     self_._keep = None
                 return {k: v[:msgs] if k in per_msg else v[:count] for k, v in out.items()}
         return _R(self.ctx, t.value, None, keep=(ring, o, ln, it, ix, rt, sl, out))
+
+
+class WireQuorum:
+    """rbc_wire_quorum (include/rbc_protocol.h): a ring of received READY
+    messages and the caller's [count][n] sender bitmap in; the bitmap with the
+    decoded READYs OR-ed in, each instance's ECHO / READY counts and its
+    RBC_QUORUM_* flags out, in one submission.  Keeps no state between calls."""
+
+    def __init__(self, ctx: Context, max_count: int, max_msgs: int, max_ring_bytes: int):
+        _lib.require_wire_ready()
+        p = c_void_p()
+        check(lib.rbc_wire_quorum_create(ctx._p, max_count, max_msgs, max_ring_bytes, byref(p)),
+              "rbc_wire_quorum_create")
+        self._p, self.ctx = p, ctx
+
+    def close(self) -> None:
+        if getattr(self, "_p", None):
+            lib.rbc_wire_quorum_destroy(self._p)
+            self._p = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def quorum(self, ready: np.ndarray, **kw) -> dict:
+        return self.submit(ready, **kw).wait()
+
+    def submit(self, ready: np.ndarray, ring: Optional[np.ndarray] = None, offs=(), lens=(), inst=(), idx=(),
+               roots=None, valid=None, status=None, self_id: int = -1,
+               ring_bytes: Optional[int] = None) -> "HostTicket":
+        """Asynchronous rbc_wire_quorum over `ready` [count][n] (uint8, updated
+        in place): message m is ring[offs[m] : offs[m] + lens[m]] (offs[m] % 16
+        == 0), a READY of the member at leaf idx[m] for instance inst[m], which
+        collects READYs for roots[inst[m]].  valid [count][n] and status [count]
+        are what WireReceiver.receive returned (or None); self_id is this node's
+        index, or -1.  No messages: only the tally.  .wait() returns verdict
+        [msgs] (the RBC_WIRE_* status), ready (the same array), echo_counts,
+        ready_counts and flags [count]."""
+        assert isinstance(ready, np.ndarray) and ready.dtype == np.uint8 and ready.flags.c_contiguous
+        assert ready.ndim == 2 and ready.shape[1] == self.ctx.n
+        msgs, count = len(offs), ready.shape[0]
+        o = np.ascontiguousarray(offs, dtype=np.uint64)
+        ln = np.ascontiguousarray(lens, dtype=np.uint32)
+        it = np.ascontiguousarray(inst, dtype=np.uint32)
+        ix = np.ascontiguousarray(idx, dtype=np.uint8)
+        assert len(ln) == msgs and len(it) == msgs and len(ix) == msgs
+        rt = va = st = None
+        if msgs:
+            assert isinstance(ring, np.ndarray) and ring.dtype == np.uint8 and ring.flags.c_contiguous
+            rt = np.ascontiguousarray(roots, dtype=np.uint8)
+            assert rt.size == count * 32
+        if valid is not None:
+            va = np.ascontiguousarray(valid, dtype=np.uint8)
+            assert va.size == count * self.ctx.n
+        if status is not None:
+            st = np.ascontiguousarray(status, dtype=np.int32)
+            assert st.size == count
+        m, c = max(msgs, 1), max(count, 1)
+        out = {"verdict": np.zeros(m, np.uint8), "ready": ready, "echo_counts": np.zeros(c, np.uint32),
+               "ready_counts": np.zeros(c, np.uint32), "flags": np.zeros(c, np.uint8)}
+        p = lambda a: None if a is None else _ptr(a)  # noqa: E731
+        t = c_uint64(0)
+        rb = 0 if not msgs else (ring.nbytes if ring_bytes is None else ring_bytes)
+        check(lib.rbc_wire_quorum(self._p, count, msgs, p(ring) if msgs else None, rb, _ptr(o), _ptr(ln), _ptr(it),
+                                  _ptr(ix), p(rt), p(va), p(st), self_id, _ptr(ready), _ptr(out["verdict"]),
+                                  _ptr(out["echo_counts"]), _ptr(out["ready_counts"]), _ptr(out["flags"]), byref(t)),
+              "rbc_wire_quorum")
+        wq = self
+
+        class _Q(HostTicket):
+            def done(self_) -> bool:
+                d = c_int(0)
+                check(lib.rbc_wire_quorum_poll(wq._p, self_.ticket, byref(d)), "rbc_wire_quorum_poll")
+                return bool(d.value)
+
+            def wait(self_) -> dict:
+                if self_._keep is not None:
+                    check(lib.rbc_wire_quorum_wait(wq._p, self_.ticket), "rbc_wire_quorum_wait")
+                    self_._keep = None
+                return {k: v[:msgs] if k == "verdict" else v[:count] for k, v in out.items()}
+        return _Q(self.ctx, t.value, None, keep=(ring, o, ln, it, ix, rt, va, st, out))
 
 
 class Encoder:

@@ -314,6 +314,110 @@ size_t rbc_val_message_size_codec(int codec, int n, uint32_t shard_len, uint32_t
 int rbc_ctx_set_wire_codec(rbc_ctx *ctx, int codec);
 int rbc_ctx_wire_codec(const rbc_ctx *ctx, int *codec);
 
+/* ---- READY from wire bytes, and the quorums of a batch of instances -------
+ * Present when RBC_HAS_WIRE_READY is defined (the ABI version stays 7: detect
+ * the addition by symbol).  READYs go in as wire bytes; per-instance counts
+ * and the protocol's decisions come out.
+ *
+ * rbc_dev_unmarshal_ready decodes `msgs` received READY messages of `count`
+ * instances into a sender bitmap.  Message m is ring[offs[m], offs[m] +
+ * lens[m]) with the rules of rbc_dev_unmarshal_echo (offs[m] % 16 == 0, no
+ * byte read outside round_up(lens[m], 16) from offs[m]); it was sent by the
+ * member at leaf idx[m] for instance inst[m], which collects READYs for
+ * roots[inst[m]].  A READY is decoded only when it is canonical: byte-for-byte
+ * what rbc_pb_encode_rbc(RBC_MSG_READY, rbc_json_encode_ready(root, 32)) emits
+ * -- one form of one length under both payload codecs (the size those two
+ * calls return), so rbc_ctx_set_wire_codec does not affect it.  A root of 31 or 33
+ * bytes encodes to as many characters: canonical requires '=' at the last
+ * base64 character and not at the one before it.  The non-zero trailing bits
+ * of the last quantum are ignored, as the host decoder ignores them.
+ * msg_status[m], decided in this order:
+ *   1. lens[m] is not that length, inst[m] >= count or idx[m] >= n (before any
+ *      byte of the message is read)                   -> RBC_WIRE_FALLBACK
+ *   2. a byte is not canonical                        -> RBC_WIRE_FALLBACK
+ *   3. the message's root (compared on the device, never stored) is not
+ *      roots[inst[m]]                                 -> RBC_WIRE_OTHER_ROOT
+ *   4. otherwise RBC_WIRE_OK, and ready[inst[m]*n + idx[m]] = 1.
+ * ready [count][n] is the caller's: the call only ever sets bytes in it, so it
+ * accumulates over calls as READYs arrive, and two messages naming one slot
+ * are harmless (both store the same 1).  A message writes nothing but
+ * msg_status[m] and that one byte.  A RBC_WIRE_FALLBACK message goes through
+ * the host decoder (rbc_pb_decode_rbc + rbc_json_decode_ready), which stays
+ * the authority on accepting it.  All pointers are device memory; ring and
+ * roots are 16-byte aligned.
+ *
+ * One limit: rbc_node counts each sender's FIRST READY, whatever its root, and
+ * rejects the sender's later ones.  This path counts every READY for
+ * roots[inst]: a sender whose first READY named another root and whose second
+ * names this one is counted here and not there.  A caller that wants the
+ * strict rule passes each sender's first READY only.  Nothing differs for
+ * honest senders, who send one. */
+#define RBC_HAS_WIRE_READY 1
+int rbc_dev_unmarshal_ready(rbc_ctx *ctx, void *stream, int count, int msgs, const uint8_t *ring,
+                            const uint64_t *offs, const uint32_t *lens, const uint32_t *inst, const uint8_t *idx,
+                            const uint8_t *roots, uint8_t *ready, int32_t *msg_status);
+
+/* The thresholds of one node (index `self`, or -1) over a batch of instances,
+ * with (n, f) the context's geometry.  Per instance i: E = the non-zero bytes
+ * of valid[i][0..n) (rbc_dev_verify's / rbc_wire_receive's valid; NULL: E = 0),
+ * R = the non-zero bytes of ready[i][0..n), st = status[i] (what
+ * rbc_dev_interpolate / rbc_wire_receive reported; NULL: nothing is known about
+ * the interpolation, and `have` is false).  rbc_node's rules over counts:
+ *   have       = st == RBC_OK && (E >= n-f || (R >= 2f+1 && E >= n-2f))
+ *   send_ready = R >= f+1 || have
+ *   if send_ready && self >= 0 && !ready[i][self]:  ready[i][self] = 1, R += 1
+ *                                       (the node's own READY counts)
+ *   deliver    = st == RBC_OK && R >= 2f+1 && E >= n-2f
+ * echo_counts[i] = E, ready_counts[i] = R after the own bit (uint32), and
+ * flags[i] holds RBC_QUORUM_ECHO (E >= n-f), RBC_QUORUM_AMPLIFY (R >= f+1
+ * before the own bit), RBC_QUORUM_SEND_READY and RBC_QUORUM_DELIVER.  The call
+ * writes ready[i][self] and nothing else of ready.  All pointers are device
+ * memory; self in [-1, n). */
+#define RBC_QUORUM_ECHO 1
+#define RBC_QUORUM_AMPLIFY 2
+#define RBC_QUORUM_SEND_READY 4
+#define RBC_QUORUM_DELIVER 8
+int rbc_dev_quorum(rbc_ctx *ctx, void *stream, int count, const uint8_t *valid, uint8_t *ready,
+                   const int32_t *status, int self, uint32_t *echo_counts, uint32_t *ready_counts, uint8_t *flags);
+
+/* Both steps from host memory in one submission.  rbc_wire_quorum_handle owns
+ * one stream and the device buffers for up to max_count instances and max_msgs
+ * messages in a ring of up to max_ring_bytes per call. */
+typedef struct rbc_wire_quorum_handle rbc_wire_quorum_handle;
+int rbc_wire_quorum_create(rbc_ctx *ctx, int max_count, int max_msgs, size_t max_ring_bytes,
+                           rbc_wire_quorum_handle **out);
+void rbc_wire_quorum_destroy(rbc_wire_quorum_handle *q); /* waits for its outstanding work */
+/* On the handle's own stream: one host-to-device copy of the metadata (with
+ * valid, status and the caller's bitmap), one of ring[0, ring_bytes) (direct
+ * DMA from rbc_host_alloc memory, staged from pageable memory),
+ * rbc_dev_unmarshal_ready, rbc_dev_quorum and one copy back:
+ *   ready_inout      [count][n]: the bitmap so far goes in; it comes back with
+ *                    the decoded READYs and the own bit OR-ed in
+ *   verdict_out[m]   (uint8) the RBC_WIRE_* status of message m
+ *   echo_counts_out, ready_counts_out [count] (uint32), flags_out [count]
+ * valid [count][n] and status [count] are host memory and nullable, as in
+ * rbc_dev_quorum.  The call keeps no state between submissions: the bitmap
+ * lives with the caller.  msgs == 0 is allowed (ring, offs, lens, inst, idx,
+ * roots and verdict_out may then be NULL): it only re-tallies, for example after new
+ * ECHO results.  count == 0 with msgs == 0 returns ticket 0.
+ * Every argument is checked before any device work, and RBC_ERR_INVALID_ARG
+ * enqueues nothing: the checks of rbc_wire_receive -- null pointers; count >
+ * max_count, msgs > max_msgs, ring_bytes > max_ring_bytes; offs[m] % 16 != 0
+ * or offs[m] + round_up(lens[m], 16) > ring_bytes; inst[m] >= count,
+ * idx[m] >= n -- except that two messages with the same (inst, idx) are
+ * allowed, and self outside [-1, n).
+ * Asynchronous: the outputs, ready_inout and the ring belong to the call until
+ * rbc_wire_quorum_wait(ticket) returns.  One submission is in flight at a
+ * time: a second rbc_wire_quorum on the same handle first completes the one
+ * before. */
+int rbc_wire_quorum(rbc_wire_quorum_handle *q, int count, int msgs, const uint8_t *ring, size_t ring_bytes,
+                    const uint64_t *offs, const uint32_t *lens, const uint32_t *inst, const uint8_t *idx,
+                    const uint8_t *roots, const uint8_t *valid, const int32_t *status, int self,
+                    uint8_t *ready_inout, uint8_t *verdict_out, uint32_t *echo_counts_out,
+                    uint32_t *ready_counts_out, uint8_t *flags_out, uint64_t *ticket);
+int rbc_wire_quorum_wait(rbc_wire_quorum_handle *q, uint64_t ticket);
+int rbc_wire_quorum_poll(rbc_wire_quorum_handle *q, uint64_t ticket, int *done);
+
 /* ---- RBC instance (one proposer's broadcast, seen at one node) ----------- */
 typedef struct rbc_node rbc_node;
 /* NewRBC (rbc/rbc.go:38). */

@@ -17,6 +17,6 @@ while [ $# -ge 2 ]; do
     wait
     /opt/rocm/bin/hipcc $FL -shared -o $ROOT/ab/librbc_gpu_$name.so $ROOT/ab/kernels_$name.o $ROOT/ab/rs_fft_$name.o \
         $ROOT/ab/gf_regen_$name.o $C/wire.o \
-        $C/capi.o $C/batcher.o $C/rbc_node.o $C/wire_rx.o $C/wire_receive.o -L/opt/rocm/lib -lrccl -Wl,-rpath,/opt/rocm/lib
+        $C/capi.o $C/batcher.o $C/rbc_node.o $C/wire_rx.o $C/wire_receive.o $C/wire_ready.o -L/opt/rocm/lib -lrccl -Wl,-rpath,/opt/rocm/lib
     echo "built ab/librbc_gpu_$name.so"
 done

@@ -16,13 +16,22 @@ pb.Message bytes in a pinned ring (a pass-through gRPC codec's view).
      rbc_interpolate_batch_kept.
   R  rbc_wire_receive: the same ring to the same values in one submission.
 
+  H  the epoch's READYs on the host: 1,024 instances x 128 READYs of 65 bytes;
+     16 threads run rbc_pb_decode_rbc + rbc_json_decode_ready, a per-sender
+     dedupe and the thresholds per instance (tools/wire_rx_decode.cpp).
+  Q  rbc_wire_quorum: the same ring to the same bitmap, counts and flags in
+     one submission.
+
 Every leg is a child process of its own under its own time limit; the parent
 stops at the first one that fails.  Each leg runs --warmup (>= 2) epochs, then
 --epochs (>= 5) timed ones, and reports the median and the min-max spread.  The
 epoch is seeded, so the legs see the same bytes, and A's and B's verdicts must
 be identical (a digest of them is compared), and so must C's and R's statuses
 and value bytes.  About 1 % of the messages carry one corrupted shard
-character, so both verdict values occur.
+character, so both verdict values occur.  H and Q see one READY ring (every
+member's READY for every instance, about 1 % with one root character replaced,
+so that READY names another root), and their bitmaps, counts, flags and
+per-message verdicts must be identical.
 
 --codec json|binary (or both, comma-separated) chooses the payload codec the
 epoch is encoded in and the context decodes (include/rbc_protocol.h,
@@ -35,6 +44,8 @@ their min-max ranges do not overlap.  Leg A is the JSON host decoder's.
   python tools/wire_rx_bench.py --legs A,B,K --out profiles/wire_rx/c2.json
   python tools/wire_rx_bench.py --legs C,R --out profiles/wire_rx/c2_receive.json
   python tools/wire_rx_bench.py --legs B,R,K --codec json,binary --out profiles/wire_rx/c2_binary.json
+  python tools/wire_rx_bench.py --legs H,Q --out profiles/wire_rx/c2_ready.json
+  python tools/wire_rx_bench.py --legs H,Q --n 256 --f 85 --instances 4096 --out profiles/wire_rx/c4_ready.json
 """
 import argparse
 import ctypes
@@ -54,7 +65,9 @@ THREADS = 16
 
 
 NAMES = {"A": "A_parent_decode_then_validate_packed_keep", "B": "B_wire_validate", "K": "K_unmarshal_kernel",
-         "C": "C_wire_validate_then_interpolate_kept", "R": "R_wire_receive"}
+         "C": "C_wire_validate_then_interpolate_kept", "R": "R_wire_receive",
+         "H": "H_host_ready_decode_and_tally", "Q": "Q_wire_quorum"}
+READY_LEGS = ("H", "Q")
 
 
 def rup(x, a):
@@ -293,13 +306,115 @@ def leg_r(ca, ctx, e, a):
     return r
 
 
+def build_ready_epoch(ca, ctx, a):
+    """The epoch's READYs in a pinned ring, ordered by instance: every member's READY for every
+    instance, ~1 % naming another root; and what the ECHO side knows (valid, status)."""
+    import numpy as np
+    from cleisthenes_amd import protocol
+    n, f, I = ctx.n, a.f, a.instances
+    rng = np.random.default_rng(a.seed)
+    roots = rng.integers(0, 256, (I, 32), dtype=np.uint8)
+    first = np.frombuffer(protocol.pb_encode(protocol.READY, protocol.json_encode_ready(roots[0].tobytes())), np.uint8)
+    mlen, slot = len(first), rup(len(first), 16)
+    count = I * n
+    ring = ca.pinned_empty(count * slot)
+    ring[:] = 0
+    r2 = ring.reshape(I, n, slot)
+    for i in range(I):
+        r2[i, :, :mlen] = np.frombuffer(protocol.pb_encode(protocol.READY, protocol.json_encode_ready(roots[i].tobytes())),
+                                        np.uint8)
+    flat = ring.reshape(count, slot)
+    root_at = bytes(first).index(b'":"') + 3  # the root's 44 base64 characters
+    for m in rng.permutation(count)[:max(count // 100, 1)]:
+        at = root_at + int(rng.integers(0, 40))
+        flat[m, at] = ord("A") if flat[m, at] != ord("A") else ord("B")
+    # the ECHO side: most instances have their N-f proven ECHOs and a value, some only N-2f, some too few
+    ecount = rng.choice([n - f, n - f, n - f, n - 2 * f, n - 2 * f - 1], I)
+    valid = np.zeros((I, n), np.uint8)
+    for i in range(I):
+        valid[i, rng.permutation(n)[:ecount[i]]] = 1
+    status = np.where(ecount >= n - 2 * f, 0, -3).astype(np.int32)
+    return {"ring": ring, "offs": np.arange(count, dtype=np.uint64) * slot, "lens": np.full(count, mlen, np.uint32),
+            "inst": np.repeat(np.arange(I, dtype=np.uint32), n), "idx": np.tile(np.arange(n, dtype=np.uint8), I),
+            "msg_first": np.arange(I + 1, dtype=np.uint32) * n, "roots": roots, "valid": valid, "status": status,
+            "count": count, "instances": I, "mlen": mlen, "S": 0, "wire_bytes": count * mlen, "shard_bytes": 0,
+            "ring_bytes": int(ring.nbytes), "self": 0}
+
+
+def ready_digest(ready, verdict, ecounts, rcounts, flags):
+    import numpy as np
+    h = hashlib.sha256()
+    for v, t in ((ready, np.uint8), (verdict, np.uint8), (ecounts, np.uint32), (rcounts, np.uint32), (flags, np.uint8)):
+        h.update(np.ascontiguousarray(v, t).tobytes())
+    return h.hexdigest()
+
+
+def ready_result(ts, e, ready, verdict, ecounts, rcounts, flags):
+    import numpy as np
+    r = stats(ts, e["wire_bytes"])
+    r.update(result_sha256=ready_digest(ready, verdict, ecounts, rcounts, flags), counted=int((verdict == 0).sum()),
+             other_root=int((verdict == 2).sum()), fallback=int((verdict == 1).sum()),
+             send_ready=int((np.asarray(flags) & 4 != 0).sum()), deliver=int((np.asarray(flags) & 8 != 0).sum()),
+             messages_per_s_median=e["count"] / statistics.median(ts))
+    return r
+
+
+def leg_h(ca, ctx, e, a):
+    import numpy as np
+    so = os.path.join(ROOT, "tools", "libwire_rx_decode.so")
+    subprocess.run(["make", "-s", "-C", os.path.join(ROOT, "tools"), "libwire_rx_decode.so"], check=True)
+    fn = ctypes.CDLL(so).wire_ready_host_range
+    fn.restype = None
+    fn.argtypes = [ctypes.c_void_p] * 5 + [ctypes.c_int] * 2 + [ctypes.c_void_p] + [ctypes.c_int] * 3 + \
+        [ctypes.c_void_p] * 7
+    I, n, count = e["instances"], ctx.n, e["count"]
+    ready, verdict = np.zeros((I, n), np.uint8), np.zeros(count, np.uint8)
+    ec, rc, fl = np.zeros(I, np.uint32), np.zeros(I, np.uint32), np.zeros(I, np.uint8)
+    edges = [I * t // THREADS for t in range(THREADS + 1)]
+    p = lambda x: x.ctypes.data  # noqa: E731
+
+    def work(t):
+        fn(p(e["ring"]), p(e["offs"]), p(e["lens"]), p(e["idx"]), p(e["msg_first"]), edges[t], edges[t + 1],
+           p(e["roots"]), n, a.f, e["self"], p(e["valid"]), p(e["status"]), p(ready), p(verdict), p(ec), p(rc), p(fl))
+
+    def epoch():
+        ready[:] = 0
+        th = [threading.Thread(target=work, args=(t,)) for t in range(THREADS)]
+        for x in th:
+            x.start()
+        for x in th:
+            x.join()
+
+    ts = timed(epoch, a.warmup, a.epochs)
+    return ready_result(ts, e, ready, verdict, ec, rc, fl)
+
+
+def leg_q(ca, ctx, e, a):
+    import numpy as np
+    I, n = e["instances"], ctx.n
+    wq = ca.WireQuorum(ctx, I, e["count"], e["ring"].nbytes)
+    ready = np.zeros((I, n), np.uint8)
+    got = {}
+
+    def epoch():
+        ready[:] = 0
+        got.update(wq.quorum(ready, ring=e["ring"], offs=e["offs"], lens=e["lens"], inst=e["inst"], idx=e["idx"],
+                             roots=e["roots"], valid=e["valid"], status=e["status"], self_id=e["self"]))
+
+    ts = timed(epoch, a.warmup, a.epochs)
+    r = ready_result(ts, e, ready, got["verdict"], got["echo_counts"], got["ready_counts"], got["flags"])
+    r.update(h2d_bytes=int(e["ring"].nbytes))
+    wq.close()
+    return r
+
+
 def child(a):
     import cleisthenes_amd as ca
     ctx = ca.Context(a.n, a.f)
     if a.codec != "json":  # before the epoch is built: the marshal kernel writes the codec's messages
         ctx.set_wire_codec(a.codec)
-    e = build_epoch(ca, ctx, a)
-    r = {"A": leg_a, "B": leg_b, "K": leg_k, "C": leg_c, "R": leg_r}[a.leg](ca, ctx, e, a)
+    e = build_ready_epoch(ca, ctx, a) if a.leg in READY_LEGS else build_epoch(ca, ctx, a)
+    r = {"A": leg_a, "B": leg_b, "K": leg_k, "C": leg_c, "R": leg_r, "H": leg_h, "Q": leg_q}[a.leg](ca, ctx, e, a)
     r.update(leg=a.leg, count=e["count"], shard_len=e["S"], message_len=e["mlen"], wire_bytes=e["wire_bytes"],
              shard_bytes=e["shard_bytes"], ring_bytes=e["ring_bytes"], codec=a.codec, library=os.path.relpath(ca.rbc.library_path(), ROOT))
     print("WIRE_RX_LEG " + json.dumps(r), flush=True)
@@ -366,7 +481,7 @@ def main():
     p.add_argument("--seed", type=int, default=20261019)
     p.add_argument("--leg-timeout", type=int, default=240, help="seconds per leg")
     p.add_argument("--out", default=None)
-    p.add_argument("--legs", default="A,B,K", help="comma-separated legs to run, of A B K C R")
+    p.add_argument("--legs", default="A,B,K", help="comma-separated legs to run, of A B K C R H Q")
     p.add_argument("--codec", default="json", help="payload codec: json, binary, or json,binary for both")
     p.add_argument("--leg", choices=list(NAMES), default=None, help=argparse.SUPPRESS)
     a = p.parse_args()
@@ -400,6 +515,13 @@ def main():
                    R_over_C_median=c["median_s"] / r["median_s"],
                    R_vs_C="win" if r["max_s"] < c["min_s"] else "loss" if r["min_s"] > c["max_s"] else "tie")
         same = same and res["results_identical"]
+    if "H" in legs and "Q" in legs:
+        h, q = legs["H"], legs["Q"]
+        res.update(ready_results_identical=h["result_sha256"] == q["result_sha256"],
+                   Q_over_H_median=h["median_s"] / q["median_s"],
+                   Q_vs_H="win" if q["max_s"] < h["min_s"] else "loss" if q["min_s"] > h["max_s"] else "tie")
+        res["geometry"].update(readies_per_instance=a.n, ready_messages=a.n * a.instances)
+        same = same and res["ready_results_identical"]
     for leg in want:
         res[NAMES[leg]] = legs[leg]
     text = json.dumps(res, indent=1)
