@@ -274,7 +274,10 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2))) void rs
     set_wave_prio(a.prio);
     constexpr int W = 1 << LOGW;
     constexpr int G = 3;   // encode: outputs are stored in groups of 2^G rows
-    constexpr int GD = 2;  // decode: compare-pipeline group (VGPRs: 1 -> 143, 2 -> 157, 3 -> 181)
+    // decode: compare groups of 2^GD rows.  N=128 VGPRs in the prefetch form
+    // (below): 1 -> 137, 2 -> 143, 3 -> 157; in the two-stage pipeline the
+    // other geometries keep: 1 -> 141, 2 -> 151 (measured: DESIGN.md 7.1)
+    constexpr int GD = 2;
     static_assert(K >= 1 && K <= N && N <= W && 2 * N > W, "geometry");
     // XCD-aware tile order: the dispatcher deals workgroups round-robin over
     // the 8 XCDs (linear id % 8), so neighbouring column tiles of one instance
@@ -319,6 +322,13 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2))) void rs
     auto row_store = [&](int pos, uint32_t x) { __builtin_amdgcn_raw_buffer_store_b32(x, rs, (int)off, pos * pitch, 0); };
     auto row_load = [&](int pos) -> uint32_t { return __builtin_amdgcn_raw_buffer_load_b32(rs, (int)off, pos * pitch, 0); };
 
+    // N=128 decode, prefetch form of the compare (below): the class bytes of
+    // the parity positions, wave-uniform, held in SGPRs from the start
+    constexpr bool PF = MODE == GF_MODE_DECODE && N == 128;
+    constexpr int CW0 = K / 4, CWN = (N + 3) / 4;
+    uint32_t cw[PF ? CWN - CW0 : 1];
+    (void)cw;
+
     uint32_t v[W];
     if constexpr (ENC) {
         const uint8_t *val = a.values + (size_t)inst * a.value_pitch;
@@ -348,6 +358,16 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2))) void rs
             row_store(j, v[j]);
         });
     } else {
+        if constexpr (PF) {
+            // issued with the row loads: one wait for all of them, and no
+            // class lookup (a dependent load and a drain of every store in
+            // flight) at each compare group later
+            const uint32_t *cls = reinterpret_cast<const uint32_t *>(a.cls + (size_t)inst * a.cls_stride);
+            lch::sfor<CW0, CWN>([&](auto J) {
+                constexpr int j = decltype(J)::value;
+                cw[j - CW0] = (uint32_t)__builtin_amdgcn_readfirstlane((int)cls[j]);
+            });
+        }
         lch::sfor<0, K>([&](auto J) { v[decltype(J)::value] = row_load(decltype(J)::value); });
         if (a.join) {
             // interpolate's value (rbc/rbc.go:88) straight from the loaded rows:
@@ -413,6 +433,53 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2))) void rs
             });
         };
         lch::fft<G, LOGW, 0, 0, K, K, N>(v, st);
+    } else if constexpr (PF) {
+        // Prefetch form.  The compare loads of the NEXT output group are
+        // issued before this group is compared and stored, and fly through
+        // the next group's butterflies; the only state carried between
+        // groups is that group's old rows (pold).  Every load is issued
+        // unconditionally -- a position that is not compared reads through a
+        // descriptor of zero records, which returns 0 without touching
+        // memory -- so the wait before a compare is a counted one that leaves
+        // the loads just issued in flight; behind a branch it would be a
+        // full drain.
+        constexpr int GS = 1 << GD;
+        uint32_t pold[GS] = {};
+        auto cls_at = [&](auto Pos) -> uint32_t {
+            constexpr int pos = decltype(Pos)::value;
+            return (cw[(pos >> 2) - CW0] >> (8 * (pos & 3))) & 0xffu;  // scalar
+        };
+        auto prefetch = [&](auto Lam, uint32_t (&dst)[GS]) {
+            constexpr int lam = decltype(Lam)::value;
+            lch::sfor<lch::cmax(K - lam, 0), lch::cmin(GS, N - lam)>([&](auto I) {
+                constexpr int i = decltype(I)::value, pos = lam + i;
+                const auto rc = __builtin_amdgcn_make_buffer_rsrc(
+                    shards, (short)0, cls_at(lch::IC<pos>{}) == 2u ? (int)a.inst_pitch : 0, 0x00020000);
+                dst[i] = __builtin_amdgcn_raw_buffer_load_b32(rc, (int)off, pos * pitch, 0);
+            });
+        };
+        auto st = [&](auto Lam, auto Off, auto Lo, auto Hi) {
+            constexpr int lam = decltype(Lam)::value, o = decltype(Off)::value;
+            constexpr int lo = lch::cmax(decltype(Lo)::value, K - lam), hi = lch::cmin(decltype(Hi)::value, N - lam);
+            if constexpr (lo < hi) {
+                uint32_t nold[GS] = {};
+                if constexpr (lam + GS < N) prefetch(lch::IC<lam + GS>{}, nold);
+                lch::sfor<lo, hi>([&](auto I) {
+                    constexpr int i = decltype(I)::value, pos = lam + i;
+                    const uint32_t c = cls_at(lch::IC<pos>{}), x = v[o + i] & keep;
+                    if (c == 1u) {
+                        row_store(pos, x);
+                    } else if (c == 2u && pold[i] != x) {
+                        row_store(pos, x);
+                        if (a.flags && atomicOr(&a.flags[(size_t)inst * N + pos], 1u) == 0u)
+                            a.list[atomicAdd(a.counter, 1u)] = ((uint32_t)inst << 8) | (uint32_t)pos;
+                    }
+                });
+                lch::sfor<0, GS>([&](auto I) { pold[decltype(I)::value] = nold[decltype(I)::value]; });
+            }
+        };
+        prefetch(lch::IC<(K / GS) * GS>{}, pold);  // the first group's, in flight through the upper layers
+        lch::fft<GD, LOGW, 0, 0, K, K, N>(v, st);
     } else {
         const uint32_t *cls = reinterpret_cast<const uint32_t *>(a.cls + (size_t)inst * a.cls_stride);
         // Software pipeline over output groups: the compare loads of group g
