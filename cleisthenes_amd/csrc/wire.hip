@@ -349,6 +349,55 @@ __device__ uint4 unb64_chunk_slow(const uint8_t *m, uint32_t off, uint32_t len, 
     return make_uint4(d[0], d[1], d[2], d[3]);
 }
 
+// branch slot r of a receiver: max(depth, 1) entries
+__device__ __forceinline__ uint8_t *branch_slot(uint8_t *branches, size_t r, int depth) {
+    return branches + r * (depth > 1 ? depth : 1) * 32u;
+}
+
+// the bits in which 16 decoded bytes of a root differ from the wanted ones
+__device__ __forceinline__ uint32_t root_diff(const uint4 &v, const uint8_t *want) {
+    const uint4 w = *reinterpret_cast<const uint4 *>(want);
+    return (v.x ^ w.x) | (v.y ^ w.y) | (v.z ^ w.z) | (v.w ^ w.w);
+}
+
+// S from rx_layout()'s L.S and the block's trailing '=': inside [0, total), the first bytes read
+__device__ __forceinline__ uint32_t rx_shard_len(const uint8_t *m, const Layout &L) {
+    const uint32_t pad = m[L.end_lit_off - 1] == '=' ? (m[L.end_lit_off - 2] == '=' ? 2u : 1u) : 0u;
+    return L.S - pad;
+}
+
+// Header, JSON literals and type field against msg_byte(): at most
+// 12 + 13 + 26 + 3 + 2 bytes, one per lane; 1 in a lane whose byte differs.
+__device__ __forceinline__ uint32_t literals_bad(const uint8_t *m, const Layout &L, uint32_t br_len, int type,
+                                                 uint32_t lane) {
+    const uint32_t head = L.hdr + 13, mid = br_len ? 24u : 26u;
+    const uint32_t nn = head + mid + 3 + (type ? 2u : 0u);
+    uint32_t bad = 0;
+    if (lane < nn) {
+        uint32_t p;
+        if (lane < head) {
+            p = lane;
+        } else {
+            const uint32_t k = lane - head;
+            if (k >= mid) p = L.end_lit_off + (k - mid);  // '"]}' and the type field behind it
+            else if (br_len && k >= 12) p = L.blk_lit_off + (k - 12);
+            else p = L.br_lit_off + k;
+        }
+        if (m[p] != msg_byte(L, p, type, nullptr, nullptr, nullptr)) bad = 1;
+    }
+    return bad;
+}
+
+// decoded bytes [o0, o0 + 16) of the run of len bytes: zeros from len on, else the fast or the slow path
+__device__ __forceinline__ uint4 unb64_chunk(const uint8_t *m, uint32_t off, uint32_t len, uint32_t o0, uint32_t &bad) {
+    uint4 v = make_uint4(0, 0, 0, 0);
+    if (o0 < len) {
+        if (4 * (o0 / 3) + 24 <= len / 3 * 4) v = unb64_chunk16(m, off, o0, bad);
+        else v = unb64_chunk_slow(m, off, len, o0, bad);
+    }
+    return v;
+}
+
 // one wave per message; 4 waves (messages) per block
 __global__ __launch_bounds__(256) void unmarshal_val_kernel(WireRxArgs a) {
     const uint32_t i = blockIdx.x * 4 + (threadIdx.x >> 6);
@@ -364,9 +413,7 @@ __global__ __launch_bounds__(256) void unmarshal_val_kernel(WireRxArgs a) {
     bool shaped = j < (uint32_t)a.n && rx_layout(total, br_len, L, type);
     uint32_t S = 0;
     if (shaped) {
-        // every offset is inside [0, total): the padding count is the only thing read so far
-        const uint32_t pad = m[L.end_lit_off - 1] == '=' ? (m[L.end_lit_off - 2] == '=' ? 2u : 1u) : 0u;
-        S = L.S - pad;
+        S = rx_shard_len(m, L);
         shaped = S <= a.row_pitch;
     }
     if (!shaped) {
@@ -378,27 +425,10 @@ __global__ __launch_bounds__(256) void unmarshal_val_kernel(WireRxArgs a) {
         return;
     }
     L.S = S;
-    uint32_t bad = 0;
-    // header, JSON literals and type field: at most 12 + 13 + 26 + 3 + 2 bytes, one per lane
-    {
-        const uint32_t head = L.hdr + 13, mid = br_len ? 24u : 26u;
-        const uint32_t nn = head + mid + 3 + (type ? 2u : 0u);
-        if (lane < nn) {
-            uint32_t p;
-            if (lane < head) {
-                p = lane;
-            } else {
-                const uint32_t k = lane - head;
-                if (k >= mid) p = L.end_lit_off + (k - mid);  // '"]}' and the type field behind it
-                else if (br_len && k >= 12) p = L.blk_lit_off + (k - 12);
-                else p = L.br_lit_off + k;
-            }
-            if (m[p] != msg_byte(L, p, type, nullptr, nullptr, nullptr)) bad = 1;
-        }
-    }
+    uint32_t bad = literals_bad(m, L, br_len, type, lane);
     // the three base64 runs, one 16-byte chunk of decoded bytes per lane-step
     const uint32_t nblk = ((S + 63u) & ~63u) >> 4, nbr = br_len >> 4, nq = nblk + nbr + 2;
-    uint8_t *slot = a.branches + (size_t)i * (a.depth > 1 ? a.depth : 1) * 32u;
+    uint8_t *slot = branch_slot(a.branches, i, a.depth);
     for (uint32_t q = lane; q < nq; q += 64) {
         uint32_t off, len, o0;
         uint8_t *dst;
@@ -412,11 +442,7 @@ __global__ __launch_bounds__(256) void unmarshal_val_kernel(WireRxArgs a) {
             off = L.root_off, len = 32, o0 = (q - nblk - nbr) << 4;
             dst = a.roots + (size_t)i * 32;
         }
-        uint4 v = make_uint4(0, 0, 0, 0);
-        if (o0 < len) {
-            if (4 * (o0 / 3) + 24 <= len / 3 * 4) v = unb64_chunk16(m, off, o0, bad);
-            else v = unb64_chunk_slow(m, off, len, o0, bad);
-        }
+        const uint4 v = unb64_chunk(m, off, len, o0, bad);
         *reinterpret_cast<uint4 *>(dst + o0) = v;
     }
     // the zero slot of an empty level-0 sibling (or of a depth-0 tree)
@@ -451,8 +477,7 @@ __global__ __launch_bounds__(256) void unmarshal_echo_kernel(WireEchoArgs a) {
     bool shaped = j < (uint32_t)a.n && in < (uint32_t)a.count && rx_layout(total, br_len, L, type);
     uint32_t S = 0;
     if (shaped) {
-        const uint32_t pad = m[L.end_lit_off - 1] == '=' ? (m[L.end_lit_off - 2] == '=' ? 2u : 1u) : 0u;
-        S = L.S - pad;
+        S = rx_shard_len(m, L);
         shaped = S <= a.shard_pitch;
     }
     if (!shaped) {
@@ -471,30 +496,13 @@ __global__ __launch_bounds__(256) void unmarshal_echo_kernel(WireEchoArgs a) {
         return;
     }
     L.S = S;
-    uint32_t bad = 0, other = 0;
-    // header, JSON literals and type field: at most 12 + 13 + 26 + 3 + 2 bytes, one per lane
-    {
-        const uint32_t head = L.hdr + 13, mid = br_len ? 24u : 26u;
-        const uint32_t nn = head + mid + 3 + (type ? 2u : 0u);
-        if (lane < nn) {
-            uint32_t p;
-            if (lane < head) {
-                p = lane;
-            } else {
-                const uint32_t k = lane - head;
-                if (k >= mid) p = L.end_lit_off + (k - mid);  // '"]}' and the type field behind it
-                else if (br_len && k >= 12) p = L.blk_lit_off + (k - 12);
-                else p = L.br_lit_off + k;
-            }
-            if (m[p] != msg_byte(L, p, type, nullptr, nullptr, nullptr)) bad = 1;
-        }
-    }
+    uint32_t bad = literals_bad(m, L, br_len, type, lane), other = 0;
     // the three base64 runs, one 16-byte chunk of decoded bytes per lane-step;
     // the two chunks of the root are compared, not stored
     const uint32_t nblk = ((S + 63u) & ~63u) >> 4, nbr = br_len >> 4, nq = nblk + nbr + 2;
     const size_t r = (size_t)in * a.n + j;
     uint8_t *row = a.shards + r * a.shard_pitch;
-    uint8_t *slot = a.branches + r * (a.depth > 1 ? a.depth : 1) * 32u;
+    uint8_t *slot = branch_slot(a.branches, r, a.depth);
     const uint8_t *want_root = a.roots + (size_t)in * 32;
     for (uint32_t q = lane; q < nq; q += 64) {
         uint32_t off, len, o0;
@@ -509,11 +517,7 @@ __global__ __launch_bounds__(256) void unmarshal_echo_kernel(WireEchoArgs a) {
             off = L.root_off, len = 32, o0 = (q - nblk - nbr) << 4;
             dst = nullptr;
         }
-        uint4 v = make_uint4(0, 0, 0, 0);
-        if (o0 < len) {
-            if (4 * (o0 / 3) + 24 <= len / 3 * 4) v = unb64_chunk16(m, off, o0, bad);
-            else v = unb64_chunk_slow(m, off, len, o0, bad);
-        }
+        const uint4 v = unb64_chunk(m, off, len, o0, bad);
         if (dst) {
             *reinterpret_cast<uint4 *>(dst + o0) = v;
         } else {
@@ -588,8 +592,7 @@ __global__ __launch_bounds__(256) void unmarshal_ready_kernel(WireReadyArgs a) {
             uint4 v;
             if (4 * (o0 / 3) + 24 <= 32 / 3 * 4) v = unb64_chunk16(msg, kReadyRoot, o0, bad);
             else v = unb64_chunk_slow(msg, kReadyRoot, 32, o0, bad);
-            const uint4 w = *reinterpret_cast<const uint4 *>(a.roots + (size_t)in * 32 + o0);
-            other = (v.x ^ w.x) | (v.y ^ w.y) | (v.z ^ w.z) | (v.w ^ w.w);
+            other = root_diff(v, a.roots + (size_t)in * 32 + o0);
         } else {
             // the header and the JSON literal in front of the root, or '"}' and the type field behind it
             const uint32_t p0 = part == 2 ? 0u : kReadyTail, p1 = part == 2 ? kReadyRoot : kReadyTotal;
@@ -849,7 +852,7 @@ __global__ __launch_bounds__(256) void unmarshal_val_bin_kernel(WireRxArgs a) {
     // root, branch and shard are any bytes: the message is canonical
     const uint32_t S = c.S, rt = (total + 15u) & ~15u;
     const uint32_t nblk = ((S + 63u) & ~63u) >> 4, nbr = 2 * L, nq = nblk + nbr + 2;
-    uint8_t *slot = a.branches + (size_t)i * (a.depth > 1 ? a.depth : 1) * 32u;
+    uint8_t *slot = branch_slot(a.branches, i, a.depth);
     for (uint32_t q = lane; q < nq; q += 64) {
         uint32_t off, len, o0;
         uint8_t *dst;
@@ -924,7 +927,7 @@ __global__ __launch_bounds__(256) void unmarshal_echo_bin_kernel(WireEchoArgs a)
     const uint32_t nblk = ((S + 63u) & ~63u) >> 4, nbr = 2 * L, nq = nblk + nbr + 2;
     const size_t r = (size_t)in * a.n + j;
     uint8_t *row = a.shards + r * a.shard_pitch;
-    uint8_t *slot = a.branches + r * (a.depth > 1 ? a.depth : 1) * 32u;
+    uint8_t *slot = branch_slot(a.branches, r, a.depth);
     const uint8_t *want_root = a.roots + (size_t)in * 32;
     uint32_t other = 0;
     for (uint32_t q = lane; q < nq; q += 64) {
@@ -935,9 +938,7 @@ __global__ __launch_bounds__(256) void unmarshal_echo_bin_kernel(WireEchoArgs a)
             *reinterpret_cast<uint4 *>(slot + (empty0 ? 32u : 0u) + o0) = bin_chunk16(m, rt, c.br_off, 32 * L, o0);
         } else {
             const uint32_t o0 = (q - nblk - nbr) << 4;
-            const uint4 v = bin_chunk16(m, rt, c.root_off, 32, o0);
-            const uint4 w = *reinterpret_cast<const uint4 *>(want_root + o0);
-            other |= (v.x ^ w.x) | (v.y ^ w.y) | (v.z ^ w.z) | (v.w ^ w.w);
+            other |= root_diff(bin_chunk16(m, rt, c.root_off, 32, o0), want_root + o0);
         }
     }
     // the zero slot of an empty level-0 sibling (or of a depth-0 tree)
@@ -998,5 +999,3 @@ hipError_t rbc_launch_marshal_val(const WireArgs &a, hipStream_t st) {
     else hipLaunchKernelGGL(marshal_val_kernel, grid, block, 0, st, a);
     return hipGetLastError();
 }
-
-

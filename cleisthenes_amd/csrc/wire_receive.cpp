@@ -7,34 +7,21 @@
 // of the ring, every shard written once.
 //
 // A translation unit of its own on the public ABI plus kernels.h, like
-// wire_rx.cpp: the host runtime (capi.cpp) does not know it.
-#include <hip/hip_runtime_api.h>
-#include <stdint.h>
+// wire_rx.cpp, with which it shares the session behind the handle (stream,
+// event, staging blocks, tickets: wire_session.h): the host runtime (capi.cpp)
+// does not know it.
 #include <string.h>
 
 #include <algorithm>
-#include <mutex>
-#include <unordered_map>
 #include <vector>
 
-#include "../../include/rbc_gpu.h"
 #include "../../include/rbc_protocol.h"
 #include "kernels.h"
+#include "wire_session.h"
+
+using namespace wire;
 
 namespace {
-
-constexpr size_t round_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
-inline bool aligned16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
-
-// one block of 16-byte aligned pieces
-struct Carver {
-    size_t o = 0;
-    size_t take(size_t n) {
-        const size_t at = o;
-        o += round_up(n, 16);
-        return at;
-    }
-};
 
 // host-to-device metadata of one call
 struct MetaIn {
@@ -65,33 +52,19 @@ struct SmallOut {
     }
 };
 
-bool host_pinned(const void *p) {
-    hipPointerAttribute_t at;
-    if (hipPointerGetAttributes(&at, p) != hipSuccess) {
-        (void)hipGetLastError();
-        return false;
-    }
-    return at.type == hipMemoryTypeHost;
-}
-
 }  // namespace
 
-struct rbc_wire_receiver {
+struct rbc_wire_receiver : WireSession {
     rbc_ctx *ctx = nullptr;
-    int n = 0, k = 0, depth = 0, device = 0, max_count = 0, max_msgs = 0;
+    int n = 0, k = 0, depth = 0, max_count = 0, max_msgs = 0;
     size_t max_ring = 0, bslot = 32;
     uint32_t pitch = 0;
-    std::mutex mu;
-    hipStream_t stream = nullptr;
-    hipEvent_t done = nullptr;
     uint8_t *d_ring = nullptr, *d_meta = nullptr, *d_small = nullptr, *d_shards = nullptr, *d_branches = nullptr,
             *d_present = nullptr, *d_leaves = nullptr, *d_values = nullptr;
     uint8_t *h_meta = nullptr, *h_small = nullptr, *h_values = nullptr;  // pinned
     std::vector<uint8_t> seen;  // [max_count][n]: the (inst, idx) pairs of the call being checked
-    uint64_t next_ticket = 1;
     // the one submission in flight
     struct {
-        uint64_t ticket = 0;
         int count = 0, msgs = 0;
         const uint32_t *inst = nullptr;  // pinned copies (h_meta)
         const uint8_t *idx = nullptr;
@@ -101,58 +74,34 @@ struct rbc_wire_receiver {
         uint8_t *verdict = nullptr, *types = nullptr, *valid = nullptr, *values = nullptr, *digests = nullptr;
         int32_t *status = nullptr;
     } cur;
-    std::unordered_map<uint64_t, int> retired;  // completed with an error, not yet waited on
 
-    void release() {
-        for (uint8_t *p : {d_ring, d_meta, d_small, d_shards, d_branches, d_present, d_leaves, d_values})
-            if (p) (void)hipFree(p);
-        for (uint8_t *p : {h_meta, h_small, h_values})
-            if (p) (void)hipHostFree(p);
-        if (stream) (void)hipStreamDestroy(stream);
-        if (done) (void)hipEventDestroy(done);
-    }
-
-    // completes the submission in flight (caller holds mu)
-    int finish() {
-        if (!cur.ticket) return RBC_OK;
-        const hipError_t e = hipEventSynchronize(done);
-        if (e == hipSuccess) {
-            const size_t count = (size_t)cur.count, msgs = (size_t)cur.msgs;
-            const SmallOut so(count, msgs, (size_t)n);
-            const int32_t *ms = reinterpret_cast<const int32_t *>(h_small + so.mstatus);
-            const uint8_t *valid = h_small + so.valid;
-            for (size_t m = 0; m < msgs; ++m) {
-                uint8_t v;
-                switch (ms[m]) {
-                case WIRE_OK: v = valid[(size_t)cur.inst[m] * n + cur.idx[m]] ? 1 : 0; break;
-                case WIRE_OTHER_ROOT: v = 0; break;
-                case WIRE_OTHER_LEN: v = 3; break;
-                default: v = 2; break;
-                }
-                cur.verdict[m] = v;
+    void copy_out() override {
+        const size_t count = (size_t)cur.count, msgs = (size_t)cur.msgs;
+        const SmallOut so(count, msgs, (size_t)n);
+        const int32_t *ms = reinterpret_cast<const int32_t *>(h_small + so.mstatus);
+        const uint8_t *valid = h_small + so.valid;
+        for (size_t m = 0; m < msgs; ++m) {
+            uint8_t v;
+            switch (ms[m]) {
+            case WIRE_OK: v = valid[(size_t)cur.inst[m] * n + cur.idx[m]] ? 1 : 0; break;
+            case WIRE_OTHER_ROOT: v = 0; break;
+            case WIRE_OTHER_LEN: v = 3; break;
+            default: v = 2; break;
             }
-            if (cur.types && msgs) memcpy(cur.types, h_small + so.types, msgs);
-            memcpy(cur.valid, valid, count * n);
-            if (cur.digests) memcpy(cur.digests, h_small + so.digests, count * 32);
-            memcpy(cur.status, h_small + so.status, count * 4);
-            for (size_t i = 0; i < count; ++i) {  // k*S_i bytes, then zeros up to value_pitch
-                uint8_t *row = cur.values + i * cur.value_pitch;
-                const size_t used = (size_t)k * cur.slens[i];
-                if (!cur.values_direct) memcpy(row, h_values + i * cur.vpitch, used);
-                memset(row + used, 0, cur.value_pitch - used);
-            }
-        } else {
-            retired[cur.ticket] = RBC_ERR_DEVICE;
+            cur.verdict[m] = v;
         }
-        cur.ticket = 0;
-        return e == hipSuccess ? RBC_OK : RBC_ERR_DEVICE;
+        if (cur.types && msgs) memcpy(cur.types, h_small + so.types, msgs);
+        memcpy(cur.valid, valid, count * n);
+        if (cur.digests) memcpy(cur.digests, h_small + so.digests, count * 32);
+        memcpy(cur.status, h_small + so.status, count * 4);
+        for (size_t i = 0; i < count; ++i) {  // k*S_i bytes, then zeros up to value_pitch
+            uint8_t *row = cur.values + i * cur.value_pitch;
+            const size_t used = (size_t)k * cur.slens[i];
+            if (!cur.values_direct) memcpy(row, h_values + i * cur.vpitch, used);
+            memset(row + used, 0, cur.value_pitch - used);
+        }
     }
 };
-
-#define RCV_HIP(expr)                                    \
-    do {                                                 \
-        if ((expr) != hipSuccess) return RBC_ERR_DEVICE; \
-    } while (0)
 
 extern "C" {
 
@@ -170,9 +119,8 @@ int rbc_dev_unmarshal_echo(rbc_ctx *ctx, void *stream, int count, int msgs, cons
     if (msgs == 0) return RBC_OK;
     if (count == 0) return RBC_ERR_INVALID_ARG;  // messages of no instance
     int k = 0, p = 0, depth = 0, device = 0;
-    if (rbc_ctx_params(ctx, &k, &p, &depth) != RBC_OK || rbc_ctx_device(ctx, &device) != RBC_OK)
-        return RBC_ERR_INVALID_ARG;
-    RCV_HIP(hipSetDevice(device));
+    if (!wire_geometry(ctx, &k, &p, &depth, &device)) return RBC_ERR_INVALID_ARG;
+    WIRE_HIP(hipSetDevice(device));
     WireEchoArgs a{};
     a.count = count;
     a.msgs = msgs;
@@ -193,7 +141,7 @@ int rbc_dev_unmarshal_echo(rbc_ctx *ctx, void *stream, int count, int msgs, cons
     a.msg_status = msg_status;
     a.types = types;
     if (rbc_ctx_wire_codec(ctx, &a.codec) != RBC_OK) return RBC_ERR_INVALID_ARG;
-    RCV_HIP(rbc_launch_unmarshal_echo(a, reinterpret_cast<hipStream_t>(stream)));
+    WIRE_HIP(rbc_launch_unmarshal_echo(a, reinterpret_cast<hipStream_t>(stream)));
     return RBC_OK;
 }
 
@@ -204,8 +152,7 @@ int rbc_wire_receiver_create(rbc_ctx *ctx, int max_count, int max_msgs, size_t m
     if (!ctx || max_count <= 0 || max_msgs <= 0 || max_ring_bytes == 0 || shard_pitch == 0 || shard_pitch % 64)
         return RBC_ERR_INVALID_ARG;
     int k = 0, p = 0, depth = 0, device = 0;
-    if (rbc_ctx_params(ctx, &k, &p, &depth) != RBC_OK || rbc_ctx_device(ctx, &device) != RBC_OK)
-        return RBC_ERR_INVALID_ARG;
+    if (!wire_geometry(ctx, &k, &p, &depth, &device)) return RBC_ERR_INVALID_ARG;
     const size_t n = (size_t)(k + p), c = (size_t)max_count;
     // rbc_dev_interpolate's bounds on one instance and one value row
     if (n * shard_pitch > 0x7fffffffULL || (size_t)k * shard_pitch > 0x7fffffffULL) return RBC_ERR_INVALID_ARG;
@@ -214,7 +161,6 @@ int rbc_wire_receiver_create(rbc_ctx *ctx, int max_count, int max_msgs, size_t m
     r->n = (int)n;
     r->k = k;
     r->depth = depth;
-    r->device = device;
     r->max_count = max_count;
     r->max_msgs = max_msgs;
     r->max_ring = max_ring_bytes;
@@ -223,35 +169,15 @@ int rbc_wire_receiver_create(rbc_ctx *ctx, int max_count, int max_msgs, size_t m
     r->seen.assign(c * n, 0);
     const size_t meta = MetaIn(c, (size_t)max_msgs).bytes, small = SmallOut(c, (size_t)max_msgs, n).bytes;
     const size_t values = c * k * shard_pitch;
-    auto dev = [](uint8_t **p, size_t bytes) { return hipMalloc(reinterpret_cast<void **>(p), bytes) == hipSuccess; };
-    auto pin = [](uint8_t **p, size_t bytes) {
-        return hipHostMalloc(reinterpret_cast<void **>(p), bytes, hipHostMallocDefault) == hipSuccess;
-    };
-    if (hipSetDevice(device) != hipSuccess ||
-        hipStreamCreateWithFlags(&r->stream, hipStreamNonBlocking) != hipSuccess ||
-        hipEventCreateWithFlags(&r->done, hipEventDisableTiming) != hipSuccess ||
-        !dev(&r->d_ring, round_up(max_ring_bytes, 16)) || !dev(&r->d_meta, meta) || !dev(&r->d_small, small) ||
-        !dev(&r->d_shards, c * n * shard_pitch) || !dev(&r->d_branches, c * n * r->bslot) ||
-        !dev(&r->d_present, c * n) || !dev(&r->d_leaves, c * n * 32) || !dev(&r->d_values, values) ||
-        !pin(&r->h_meta, meta) || !pin(&r->h_small, small) || !pin(&r->h_values, values)) {
-        r->release();
-        delete r;
-        return RBC_ERR_DEVICE;
-    }
-    *out = r;
-    return RBC_OK;
+    const bool ok = r->open(device) && r->dev(&r->d_ring, round_up(max_ring_bytes, 16)) && r->dev(&r->d_meta, meta) &&
+                    r->dev(&r->d_small, small) && r->dev(&r->d_shards, c * n * shard_pitch) &&
+                    r->dev(&r->d_branches, c * n * r->bslot) && r->dev(&r->d_present, c * n) &&
+                    r->dev(&r->d_leaves, c * n * 32) && r->dev(&r->d_values, values) && r->pin(&r->h_meta, meta) &&
+                    r->pin(&r->h_small, small) && r->pin(&r->h_values, values);
+    return session_created(r, ok, out);
 }
 
-void rbc_wire_receiver_destroy(rbc_wire_receiver *r) {
-    if (!r) return;
-    {
-        std::lock_guard<std::mutex> lk(r->mu);
-        (void)hipSetDevice(r->device);
-        (void)r->finish();
-        r->release();
-    }
-    delete r;
-}
+void rbc_wire_receiver_destroy(rbc_wire_receiver *r) { session_destroy(r); }
 
 int rbc_wire_receive(rbc_wire_receiver *r, int count, int msgs, const uint8_t *ring, size_t ring_bytes,
                      const uint64_t *offs, const uint32_t *lens, const uint32_t *inst, const uint8_t *idx,
@@ -282,9 +208,7 @@ int rbc_wire_receive(rbc_wire_receiver *r, int count, int msgs, const uint8_t *r
         int marked = 0;  // messages [0, marked) have their slot marked in the bitmap
         for (; marked < msgs; ++marked) {
             const int m = marked;
-            if (offs[m] % 16 || offs[m] > ring_bytes || round_up((size_t)lens[m], 16) > ring_bytes - offs[m] ||
-                inst[m] >= (uint32_t)count || idx[m] >= n)
-                break;
+            if (!ring_slot_ok(offs[m], lens[m], ring_bytes, idx[m], n, inst[m], (uint32_t)count)) break;
             uint8_t &s = r->seen[(size_t)inst[m] * n + idx[m]];
             if (s) break;  // two messages for one slot
             s = 1;
@@ -292,8 +216,7 @@ int rbc_wire_receive(rbc_wire_receiver *r, int count, int msgs, const uint8_t *r
         for (int q = 0; q < marked; ++q) r->seen[(size_t)inst[q] * n + idx[q]] = 0;
         if (marked < msgs) return RBC_ERR_INVALID_ARG;
     }
-    RCV_HIP(hipSetDevice(r->device));
-    (void)r->finish();  // the staging blocks are free again (its status stays with its ticket)
+    if (r->begin() != RBC_OK) return RBC_ERR_DEVICE;  // the one in flight keeps its status with its ticket
     hipStream_t st = r->stream;
     const size_t c = (size_t)count, mm = (size_t)msgs;
     const MetaIn mi(c, mm);
@@ -307,10 +230,10 @@ int rbc_wire_receive(rbc_wire_receiver *r, int count, int msgs, const uint8_t *r
     memcpy(r->h_meta + mi.roots, roots, c * 32);
     uint32_t *h_slens = reinterpret_cast<uint32_t *>(r->h_meta + mi.slens);
     for (int i = 0; i < count; ++i) h_slens[i] = (uint32_t)shard_lens[i];
-    RCV_HIP(hipMemcpyAsync(r->d_meta, r->h_meta, mi.bytes, hipMemcpyHostToDevice, st));
-    if (msgs) RCV_HIP(hipMemcpyAsync(r->d_ring, ring, ring_bytes, hipMemcpyHostToDevice, st));
-    RCV_HIP(hipMemsetAsync(r->d_present, 0, c * n, st));
-    RCV_HIP(hipMemsetAsync(r->d_shards, 0, c * n * r->pitch, st));
+    WIRE_HIP(hipMemcpyAsync(r->d_meta, r->h_meta, mi.bytes, hipMemcpyHostToDevice, st));
+    if (msgs) WIRE_HIP(hipMemcpyAsync(r->d_ring, ring, ring_bytes, hipMemcpyHostToDevice, st));
+    WIRE_HIP(hipMemsetAsync(r->d_present, 0, c * n, st));
+    WIRE_HIP(hipMemsetAsync(r->d_shards, 0, c * n * r->pitch, st));
     const uint8_t *d_roots = r->d_meta + mi.roots;
     const uint32_t *d_slens = reinterpret_cast<const uint32_t *>(r->d_meta + mi.slens);
     int32_t *d_mstatus = reinterpret_cast<int32_t *>(r->d_small + so.mstatus);
@@ -328,7 +251,7 @@ int rbc_wire_receive(rbc_wire_receiver *r, int count, int msgs, const uint8_t *r
                         d_valid, r->d_leaves);
     if (rc) return rc;
     const size_t vpitch = round_up(k * Smax, 16);
-    RCV_HIP(hipMemsetAsync(r->d_values, 0, c * vpitch, st));
+    WIRE_HIP(hipMemsetAsync(r->d_values, 0, c * vpitch, st));
     rc = rbc_dev_interpolate(r->ctx, st, count, r->d_shards, r->pitch, d_slens, 0, d_valid, r->d_leaves, 1, d_roots,
                              r->d_values, (uint32_t)vpitch, d_digests, d_status);
     if (rc) return rc;
@@ -336,10 +259,9 @@ int rbc_wire_receive(rbc_wire_receiver *r, int count, int msgs, const uint8_t *r
     const bool direct = value_pitch == vpitch && host_pinned(values_out) &&
                         host_pinned(values_out + (c - 1) * value_pitch + k * Smax - 1);
     const size_t vbytes = (c - 1) * vpitch + k * Smax;
-    RCV_HIP(hipMemcpyAsync(direct ? values_out : r->h_values, r->d_values, vbytes, hipMemcpyDeviceToHost, st));
-    RCV_HIP(hipMemcpyAsync(r->h_small, r->d_small, so.bytes, hipMemcpyDeviceToHost, st));
-    RCV_HIP(hipEventRecord(r->done, st));
-    r->cur.ticket = r->next_ticket++;
+    WIRE_HIP(hipMemcpyAsync(direct ? values_out : r->h_values, r->d_values, vbytes, hipMemcpyDeviceToHost, st));
+    WIRE_HIP(hipMemcpyAsync(r->h_small, r->d_small, so.bytes, hipMemcpyDeviceToHost, st));
+    WIRE_HIP(hipEventRecord(r->done, st));
     r->cur.count = count;
     r->cur.msgs = msgs;
     r->cur.inst = reinterpret_cast<const uint32_t *>(r->h_meta + mi.inst);
@@ -354,37 +276,12 @@ int rbc_wire_receive(rbc_wire_receiver *r, int count, int msgs, const uint8_t *r
     r->cur.values = values_out;
     r->cur.digests = digests_out;
     r->cur.status = status_out;
-    *ticket = r->cur.ticket;
+    *ticket = r->issue();
     return RBC_OK;
 }
 
-int rbc_wire_receive_wait(rbc_wire_receiver *r, uint64_t ticket) {
-    if (!r) return RBC_ERR_INVALID_ARG;
-    if (ticket == 0) return RBC_OK;
-    std::lock_guard<std::mutex> lk(r->mu);
-    if (ticket >= r->next_ticket) return RBC_ERR_INVALID_ARG;
-    if (ticket == r->cur.ticket) {
-        RCV_HIP(hipSetDevice(r->device));
-        (void)r->finish();
-    }
-    auto it = r->retired.find(ticket);
-    if (it == r->retired.end()) return RBC_OK;
-    const int rc = it->second;
-    r->retired.erase(it);
-    return rc;
-}
+int rbc_wire_receive_wait(rbc_wire_receiver *r, uint64_t ticket) { return session_wait(r, ticket); }
 
-int rbc_wire_receive_poll(rbc_wire_receiver *r, uint64_t ticket, int *done) {
-    if (!r || !done) return RBC_ERR_INVALID_ARG;
-    std::lock_guard<std::mutex> lk(r->mu);
-    if (ticket >= r->next_ticket) return RBC_ERR_INVALID_ARG;
-    *done = 1;
-    if (ticket && ticket == r->cur.ticket) {
-        const hipError_t e = hipEventQuery(r->done);
-        if (e == hipErrorNotReady) *done = 0;
-        else if (e != hipSuccess) return RBC_ERR_DEVICE;
-    }
-    return RBC_OK;
-}
+int rbc_wire_receive_poll(rbc_wire_receiver *r, uint64_t ticket, int *done) { return session_poll(r, ticket, done); }
 
 }  // extern "C"

@@ -6,41 +6,32 @@
 // for rbc_interpolate_batch_kept.
 //
 // A translation unit of its own on the public ABI plus kernels.h, like the
-// batcher: the host runtime (capi.cpp) does not know it.
-#include <hip/hip_runtime_api.h>
-#include <stdint.h>
+// batcher: the host runtime (capi.cpp) does not know it.  The session behind
+// the handle (stream, event, staging blocks, tickets) is wire_session.h's,
+// shared with wire_receive.cpp and wire_ready.cpp.
 #include <string.h>
 
-#include <mutex>
-#include <unordered_map>
-
-#include "../../include/rbc_gpu.h"
 #include "../../include/rbc_protocol.h"
 #include "kernels.h"
+#include "wire_session.h"
+
+using namespace wire;
 
 namespace {
-
-constexpr size_t round_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
-inline bool aligned16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
 
 // where the small outputs of `count` messages sit in the one block that
 // crosses back to the host
 struct SmallOut {
     size_t valid, types, status, slens, roots, leaves, bytes;
     explicit SmallOut(size_t count) {
-        size_t o = 0;
-        auto take = [&o](size_t n) {
-            const size_t at = o;
-            o += round_up(n, 16);
-            return at;
-        };
-        valid = take(count);
-        types = take(count);
-        status = take(count * 4);
-        slens = take(count * 4);
-        roots = take(count * 32);
-        leaves = take(count * 32);
-        bytes = o;
+        Carver c;
+        valid = c.take(count);
+        types = c.take(count);
+        status = c.take(count * 4);
+        slens = c.take(count * 4);
+        roots = c.take(count * 32);
+        leaves = c.take(count * 32);
+        bytes = c.o;
     }
 };
 
@@ -48,69 +39,41 @@ struct SmallOut {
 struct MetaIn {
     size_t offs, lens, idx, bytes;
     explicit MetaIn(size_t count) {
-        offs = 0;
-        lens = round_up(count * 8, 16);
-        idx = lens + round_up(count * 4, 16);
-        bytes = idx + round_up(count, 16);
+        Carver c;
+        offs = c.take(count * 8);
+        lens = c.take(count * 4);
+        idx = c.take(count);
+        bytes = c.o;
     }
 };
 
 }  // namespace
 
-struct rbc_wire_rx {
+struct rbc_wire_rx : WireSession {
     rbc_ctx *ctx = nullptr;
-    int n = 0, depth = 0, device = 0, max_msgs = 0;
+    int n = 0, depth = 0, max_msgs = 0;
     size_t max_ring = 0, bslot = 32;
     uint32_t row_pitch = 0;
-    std::mutex mu;
-    hipStream_t stream = nullptr;
-    hipEvent_t done = nullptr;
     uint8_t *d_ring = nullptr, *d_meta = nullptr, *d_small = nullptr, *d_branches = nullptr;
     uint8_t *h_meta = nullptr, *h_small = nullptr;  // pinned
-    uint64_t next_ticket = 1;
     // the one submission in flight
     struct {
-        uint64_t ticket = 0;
         int count = 0;
         uint8_t *verdict = nullptr, *types = nullptr, *roots = nullptr, *leaves = nullptr;
         uint32_t *slens = nullptr;
     } cur;
-    std::unordered_map<uint64_t, int> retired;  // completed with an error, not yet waited on
 
-    void release() {
-        for (uint8_t *p : {d_ring, d_meta, d_small, d_branches})
-            if (p) (void)hipFree(p);
-        for (uint8_t *p : {h_meta, h_small})
-            if (p) (void)hipHostFree(p);
-        if (stream) (void)hipStreamDestroy(stream);
-        if (done) (void)hipEventDestroy(done);
-    }
-
-    // completes the submission in flight (caller holds mu)
-    int finish() {
-        if (!cur.ticket) return RBC_OK;
+    void copy_out() override {
         const int count = cur.count;
-        const hipError_t e = hipEventSynchronize(done);
-        if (e == hipSuccess) {
-            const SmallOut so((size_t)count);
-            const int32_t *status = reinterpret_cast<const int32_t *>(h_small + so.status);
-            for (int i = 0; i < count; ++i) cur.verdict[i] = status[i] != WIRE_OK ? 2 : (h_small[so.valid + i] ? 1 : 0);
-            if (cur.types) memcpy(cur.types, h_small + so.types, (size_t)count);
-            if (cur.slens) memcpy(cur.slens, h_small + so.slens, (size_t)count * 4);
-            if (cur.roots) memcpy(cur.roots, h_small + so.roots, (size_t)count * 32);
-            if (cur.leaves) memcpy(cur.leaves, h_small + so.leaves, (size_t)count * 32);
-        } else {
-            retired[cur.ticket] = RBC_ERR_DEVICE;
-        }
-        cur.ticket = 0;
-        return e == hipSuccess ? RBC_OK : RBC_ERR_DEVICE;
+        const SmallOut so((size_t)count);
+        const int32_t *status = reinterpret_cast<const int32_t *>(h_small + so.status);
+        for (int i = 0; i < count; ++i) cur.verdict[i] = status[i] != WIRE_OK ? 2 : (h_small[so.valid + i] ? 1 : 0);
+        if (cur.types) memcpy(cur.types, h_small + so.types, (size_t)count);
+        if (cur.slens) memcpy(cur.slens, h_small + so.slens, (size_t)count * 4);
+        if (cur.roots) memcpy(cur.roots, h_small + so.roots, (size_t)count * 32);
+        if (cur.leaves) memcpy(cur.leaves, h_small + so.leaves, (size_t)count * 32);
     }
 };
-
-#define RX_HIP(expr)                                  \
-    do {                                              \
-        if ((expr) != hipSuccess) return RBC_ERR_DEVICE; \
-    } while (0)
 
 extern "C" {
 
@@ -126,9 +89,8 @@ int rbc_dev_unmarshal_val(rbc_ctx *ctx, void *stream, int count, const uint8_t *
         return RBC_ERR_INVALID_ARG;
     if (count == 0) return RBC_OK;
     int k = 0, p = 0, depth = 0, device = 0;
-    if (rbc_ctx_params(ctx, &k, &p, &depth) != RBC_OK || rbc_ctx_device(ctx, &device) != RBC_OK)
-        return RBC_ERR_INVALID_ARG;
-    RX_HIP(hipSetDevice(device));
+    if (!wire_geometry(ctx, &k, &p, &depth, &device)) return RBC_ERR_INVALID_ARG;
+    WIRE_HIP(hipSetDevice(device));
     WireRxArgs a{};
     a.count = count;
     a.n = k + p;
@@ -145,7 +107,7 @@ int rbc_dev_unmarshal_val(rbc_ctx *ctx, void *stream, int count, const uint8_t *
     a.types = types_out;
     a.status = status_out;
     if (rbc_ctx_wire_codec(ctx, &a.codec) != RBC_OK) return RBC_ERR_INVALID_ARG;
-    RX_HIP(rbc_launch_unmarshal_val(a, reinterpret_cast<hipStream_t>(stream)));
+    WIRE_HIP(rbc_launch_unmarshal_val(a, reinterpret_cast<hipStream_t>(stream)));
     return RBC_OK;
 }
 
@@ -154,46 +116,25 @@ int rbc_wire_rx_create(rbc_ctx *ctx, int max_msgs, size_t max_ring_bytes, uint32
     *out = nullptr;
     if (!ctx || max_msgs <= 0 || max_ring_bytes == 0 || row_pitch == 0 || row_pitch % 64) return RBC_ERR_INVALID_ARG;
     int k = 0, p = 0, depth = 0, device = 0;
-    if (rbc_ctx_params(ctx, &k, &p, &depth) != RBC_OK || rbc_ctx_device(ctx, &device) != RBC_OK)
-        return RBC_ERR_INVALID_ARG;
+    if (!wire_geometry(ctx, &k, &p, &depth, &device)) return RBC_ERR_INVALID_ARG;
     rbc_wire_rx *rx = new rbc_wire_rx();
     rx->ctx = ctx;
     rx->n = k + p;
     rx->depth = depth;
-    rx->device = device;
     rx->max_msgs = max_msgs;
     rx->max_ring = max_ring_bytes;
     rx->row_pitch = row_pitch;
     rx->bslot = (size_t)(depth > 1 ? depth : 1) * 32;
     const size_t m = (size_t)max_msgs;
     const size_t meta = MetaIn(m).bytes, small = SmallOut(m).bytes;
-    if (hipSetDevice(device) != hipSuccess ||
-        hipStreamCreateWithFlags(&rx->stream, hipStreamNonBlocking) != hipSuccess ||
-        hipEventCreateWithFlags(&rx->done, hipEventDisableTiming) != hipSuccess ||
-        hipMalloc(reinterpret_cast<void **>(&rx->d_ring), round_up(max_ring_bytes, 16)) != hipSuccess ||
-        hipMalloc(reinterpret_cast<void **>(&rx->d_meta), meta) != hipSuccess ||
-        hipMalloc(reinterpret_cast<void **>(&rx->d_small), small) != hipSuccess ||
-        hipMalloc(reinterpret_cast<void **>(&rx->d_branches), m * rx->bslot) != hipSuccess ||
-        hipHostMalloc(reinterpret_cast<void **>(&rx->h_meta), meta, hipHostMallocDefault) != hipSuccess ||
-        hipHostMalloc(reinterpret_cast<void **>(&rx->h_small), small, hipHostMallocDefault) != hipSuccess) {
-        rx->release();
-        delete rx;
-        return RBC_ERR_DEVICE;
-    }
-    *out = rx;
-    return RBC_OK;
+    const bool ok = rx->open(device) && rx->dev(&rx->d_ring, round_up(max_ring_bytes, 16)) &&
+                    rx->dev(&rx->d_meta, meta) && rx->dev(&rx->d_small, small) &&
+                    rx->dev(&rx->d_branches, m * rx->bslot) && rx->pin(&rx->h_meta, meta) &&
+                    rx->pin(&rx->h_small, small);
+    return session_created(rx, ok, out);
 }
 
-void rbc_wire_rx_destroy(rbc_wire_rx *rx) {
-    if (!rx) return;
-    {
-        std::lock_guard<std::mutex> lk(rx->mu);
-        (void)hipSetDevice(rx->device);
-        (void)rx->finish();
-        rx->release();
-    }
-    delete rx;
-}
+void rbc_wire_rx_destroy(rbc_wire_rx *rx) { session_destroy(rx); }
 
 int rbc_wire_validate(rbc_wire_rx *rx, int count, const uint8_t *ring, size_t ring_bytes, const uint64_t *offs,
                       const uint32_t *lens, const uint8_t *idx, uint8_t *verdict_out, uint8_t *types_out,
@@ -211,34 +152,24 @@ int rbc_wire_validate(rbc_wire_rx *rx, int count, const uint8_t *ring, size_t ri
     if (keep_bytes / rx->row_pitch < (size_t)count || !aligned16(keep_dev)) return RBC_ERR_INVALID_ARG;
     // every message's 16-byte chunks inside the ring (no wrap-around), its leaf inside the tree
     for (int i = 0; i < count; ++i) {
-        if (offs[i] % 16 || offs[i] > ring_bytes || round_up((size_t)lens[i], 16) > ring_bytes - offs[i] ||
-            idx[i] >= rx->n)
-            return RBC_ERR_INVALID_ARG;
+        if (!ring_slot_ok(offs[i], lens[i], ring_bytes, idx[i], (size_t)rx->n)) return RBC_ERR_INVALID_ARG;
     }
-    {  // both ends of the kept rows: device memory of the context's device
-        const size_t span = (size_t)count * rx->row_pitch;
-        for (const uint8_t *q : {keep_dev, keep_dev + span - 1}) {
-            hipPointerAttribute_t at;
-            if (hipPointerGetAttributes(&at, q) != hipSuccess) {
-                (void)hipGetLastError();
-                return RBC_ERR_INVALID_ARG;
-            }
-            if (at.type != hipMemoryTypeDevice || at.device != rx->device) return RBC_ERR_INVALID_ARG;
-        }
-    }
+    // both ends of the kept rows: device memory of the context's device
+    if (!device_memory(keep_dev, rx->device) ||
+        !device_memory(keep_dev + (size_t)count * rx->row_pitch - 1, rx->device))
+        return RBC_ERR_INVALID_ARG;
     int codec = 0;  // the context's payload codec, read at submission
     if (rbc_ctx_wire_codec(rx->ctx, &codec) != RBC_OK) return RBC_ERR_INVALID_ARG;
     std::lock_guard<std::mutex> lk(rx->mu);
-    RX_HIP(hipSetDevice(rx->device));
-    (void)rx->finish();  // the staging blocks are free again (its status stays with its ticket)
+    if (rx->begin() != RBC_OK) return RBC_ERR_DEVICE;  // the one in flight keeps its status with its ticket
     hipStream_t st = rx->stream;
     const MetaIn mi((size_t)count);
     const SmallOut so((size_t)count);
     memcpy(rx->h_meta + mi.offs, offs, (size_t)count * 8);
     memcpy(rx->h_meta + mi.lens, lens, (size_t)count * 4);
     memcpy(rx->h_meta + mi.idx, idx, (size_t)count);
-    RX_HIP(hipMemcpyAsync(rx->d_meta, rx->h_meta, mi.bytes, hipMemcpyHostToDevice, st));
-    RX_HIP(hipMemcpyAsync(rx->d_ring, ring, ring_bytes, hipMemcpyHostToDevice, st));
+    WIRE_HIP(hipMemcpyAsync(rx->d_meta, rx->h_meta, mi.bytes, hipMemcpyHostToDevice, st));
+    WIRE_HIP(hipMemcpyAsync(rx->d_ring, ring, ring_bytes, hipMemcpyHostToDevice, st));
     WireRxArgs u{};
     u.count = count;
     u.n = rx->n;
@@ -255,7 +186,7 @@ int rbc_wire_validate(rbc_wire_rx *rx, int count, const uint8_t *ring, size_t ri
     u.types = rx->d_small + so.types;
     u.status = reinterpret_cast<int32_t *>(rx->d_small + so.status);
     u.codec = codec;
-    RX_HIP(rbc_launch_unmarshal_val(u, st));
+    WIRE_HIP(rbc_launch_unmarshal_val(u, st));
     // validateMessage per decoded message (fallback messages are skipped by their status)
     ShaArgs a{};
     a.count = count;
@@ -276,47 +207,21 @@ int rbc_wire_validate(rbc_wire_rx *rx, int count, const uint8_t *ring, size_t ri
     a.valid = rx->d_small + so.valid;
     a.leaves = rx->d_small + so.leaves;
     a.leaves_inst_pitch = 32;
-    RX_HIP(rbc_launch_sha_rows(a, true, st));
-    RX_HIP(hipMemcpyAsync(rx->h_small, rx->d_small, so.bytes, hipMemcpyDeviceToHost, st));
-    RX_HIP(hipEventRecord(rx->done, st));
-    rx->cur.ticket = rx->next_ticket++;
+    WIRE_HIP(rbc_launch_sha_rows(a, true, st));
+    WIRE_HIP(hipMemcpyAsync(rx->h_small, rx->d_small, so.bytes, hipMemcpyDeviceToHost, st));
+    WIRE_HIP(hipEventRecord(rx->done, st));
     rx->cur.count = count;
     rx->cur.verdict = verdict_out;
     rx->cur.types = types_out;
     rx->cur.roots = roots_out;
     rx->cur.slens = shard_lens_out;
     rx->cur.leaves = leaves_out;
-    *ticket = rx->cur.ticket;
+    *ticket = rx->issue();
     return RBC_OK;
 }
 
-int rbc_wire_wait(rbc_wire_rx *rx, uint64_t ticket) {
-    if (!rx) return RBC_ERR_INVALID_ARG;
-    if (ticket == 0) return RBC_OK;
-    std::lock_guard<std::mutex> lk(rx->mu);
-    if (ticket >= rx->next_ticket) return RBC_ERR_INVALID_ARG;
-    if (ticket == rx->cur.ticket) {
-        RX_HIP(hipSetDevice(rx->device));
-        (void)rx->finish();
-    }
-    auto it = rx->retired.find(ticket);
-    if (it == rx->retired.end()) return RBC_OK;
-    const int rc = it->second;
-    rx->retired.erase(it);
-    return rc;
-}
+int rbc_wire_wait(rbc_wire_rx *rx, uint64_t ticket) { return session_wait(rx, ticket); }
 
-int rbc_wire_poll(rbc_wire_rx *rx, uint64_t ticket, int *done) {
-    if (!rx || !done) return RBC_ERR_INVALID_ARG;
-    std::lock_guard<std::mutex> lk(rx->mu);
-    if (ticket >= rx->next_ticket) return RBC_ERR_INVALID_ARG;
-    *done = 1;
-    if (ticket && ticket == rx->cur.ticket) {
-        const hipError_t e = hipEventQuery(rx->done);
-        if (e == hipErrorNotReady) *done = 0;
-        else if (e != hipSuccess) return RBC_ERR_DEVICE;
-    }
-    return RBC_OK;
-}
+int rbc_wire_poll(rbc_wire_rx *rx, uint64_t ticket, int *done) { return session_poll(rx, ticket, done); }
 
 }  // extern "C"

@@ -828,19 +828,20 @@ class Context:
         return out
 
 
-class WireRx:
-    """rbc_wire_rx (include/rbc_protocol.h): ECHOs validated straight from
-    their wire bytes, the shards kept on the device."""
+class _WireHandle:
+    """What the three wire handles share: the C handle `_p` made by the
+    subclass's create function, its context, and close() through its destroy
+    function."""
+    _create = _destroy = ""
 
-    def __init__(self, ctx: Context, max_msgs: int, max_ring_bytes: int, row_pitch: int):
-        _lib.require_wire_rx()
+    def __init__(self, ctx: Context, *args):
         p = c_void_p()
-        check(lib.rbc_wire_rx_create(ctx._p, max_msgs, max_ring_bytes, row_pitch, byref(p)), "rbc_wire_rx_create")
-        self._p, self.ctx, self.row_pitch = p, ctx, row_pitch
+        check(getattr(lib, self._create)(ctx._p, *args, byref(p)), self._create)
+        self._p, self.ctx = p, ctx
 
     def close(self) -> None:
         if getattr(self, "_p", None):
-            lib.rbc_wire_rx_destroy(self._p)
+            getattr(lib, self._destroy)(self._p)
             self._p = None
 
     def __del__(self):
@@ -848,6 +849,39 @@ class WireRx:
             self.close()
         except Exception:
             pass
+
+
+class _WireTicket(HostTicket):
+    """A submission of a wire handle, polled and waited on with the handle's own
+    pair of functions.  wait() returns the outputs named in per_msg trimmed to
+    `msgs` entries and the others to `count`."""
+
+    def __init__(self, handle, poll, wait, ticket, out, msgs, count, per_msg, keep):
+        super().__init__(handle.ctx, ticket, None, keep)
+        self._handle, self._poll, self._wait = handle, poll, wait
+        self._out, self._msgs, self._count, self._per_msg = out, msgs, count, per_msg
+
+    def done(self) -> bool:
+        d = c_int(0)
+        check(getattr(lib, self._poll)(self._handle._p, self.ticket, byref(d)), self._poll)
+        return bool(d.value)
+
+    def wait(self) -> dict:
+        if self._keep is not None:
+            check(getattr(lib, self._wait)(self._handle._p, self.ticket), self._wait)
+            self._keep = None
+        return {k: v[:self._msgs] if k in self._per_msg else v[:self._count] for k, v in self._out.items()}
+
+
+class WireRx(_WireHandle):
+    """rbc_wire_rx (include/rbc_protocol.h): ECHOs validated straight from
+    their wire bytes, the shards kept on the device."""
+    _create, _destroy = "rbc_wire_rx_create", "rbc_wire_rx_destroy"
+
+    def __init__(self, ctx: Context, max_msgs: int, max_ring_bytes: int, row_pitch: int):
+        _lib.require_wire_rx()
+        super().__init__(ctx, max_msgs, max_ring_bytes, row_pitch)
+        self.row_pitch = row_pitch
 
     def validate(self, ring: np.ndarray, offs, lens, idx, keep: DeviceBuffer, ring_bytes: Optional[int] = None) -> dict:
         return self.validate_submit(ring, offs, lens, idx, keep, ring_bytes).wait()
@@ -872,45 +906,21 @@ class WireRx:
                                     _ptr(o), _ptr(ln), _ptr(ix), _ptr(out["verdict"]), _ptr(out["types"]),
                                     _ptr(out["roots"]), _ptr(out["shard_lens"]), _ptr(out["leaves"]), keep.ptr,
                                     keep.nbytes, byref(t)), "rbc_wire_validate")
-        rx = self
-
-        class _W(HostTicket):
-            def done(self_) -> bool:
-                d = c_int(0)
-                check(lib.rbc_wire_poll(rx._p, self_.ticket, byref(d)), "rbc_wire_poll")
-                return bool(d.value)
-
-            def wait(self_) -> dict:
-                if self_._keep is not None:
-                    check(lib.rbc_wire_wait(rx._p, self_.ticket), "rbc_wire_wait")
-                    self_._keep = None
-                return {k: v[:count] for k, v in out.items()}
-        return _W(self.ctx, t.value, None, keep=(ring, o, ln, ix, out, keep))
+        return _WireTicket(self, "rbc_wire_poll", "rbc_wire_wait", t.value, out, count, count, (),
+                           keep=(ring, o, ln, ix, out, keep))
 
 
-class WireReceiver:
+class WireReceiver(_WireHandle):
     """rbc_wire_receiver (include/rbc_protocol.h): a ring of received ECHO
     messages in, every instance's value, digest and status out, in one
     submission.  While one is in flight the context must not run dev_verify,
     dev_interpolate or dev_receive_step work on another stream."""
+    _create, _destroy = "rbc_wire_receiver_create", "rbc_wire_receiver_destroy"
 
     def __init__(self, ctx: Context, max_count: int, max_msgs: int, max_ring_bytes: int, shard_pitch: int):
         _lib.require_wire_receive()
-        p = c_void_p()
-        check(lib.rbc_wire_receiver_create(ctx._p, max_count, max_msgs, max_ring_bytes, shard_pitch, byref(p)),
-              "rbc_wire_receiver_create")
-        self._p, self.ctx, self.shard_pitch = p, ctx, shard_pitch
-
-    def close(self) -> None:
-        if getattr(self, "_p", None):
-            lib.rbc_wire_receiver_destroy(self._p)
-            self._p = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+        super().__init__(ctx, max_count, max_msgs, max_ring_bytes, shard_pitch)
+        self.shard_pitch = shard_pitch
 
     def receive(self, ring: np.ndarray, offs, lens, inst, idx, roots, shard_lens, **kw) -> dict:
         return self.receive_submit(ring, offs, lens, inst, idx, roots, shard_lens, **kw).wait()
@@ -947,46 +957,20 @@ class WireReceiver:
                                    _ptr(out["types"]), _ptr(out["valid"]), _ptr(values), values.strides[0],
                                    _ptr(out["digests"]), out["status"].ctypes.data_as(_lib.i32p), byref(t)),
               "rbc_wire_receive")
-        rcv = self
-        per_msg = ("verdict", "types")
-
-        class _R(HostTicket):
-            def done(self_) -> bool:
-                d = c_int(0)
-                check(lib.rbc_wire_receive_poll(rcv._p, self_.ticket, byref(d)), "rbc_wire_receive_poll")
-                return bool(d.value)
-
-            def wait(self_) -> dict:
-                if self_._keep is not None:
-                    check(lib.rbc_wire_receive_wait(rcv._p, self_.ticket), "rbc_wire_receive_wait")
-                    self_._keep = None
-                return {k: v[:msgs] if k in per_msg else v[:count] for k, v in out.items()}
-        return _R(self.ctx, t.value, None, keep=(ring, o, ln, it, ix, rt, sl, out))
+        return _WireTicket(self, "rbc_wire_receive_poll", "rbc_wire_receive_wait", t.value, out, msgs, count,
+                           ("verdict", "types"), keep=(ring, o, ln, it, ix, rt, sl, out))
 
 
-class WireQuorum:
+class WireQuorum(_WireHandle):
     """rbc_wire_quorum (include/rbc_protocol.h): a ring of received READY
     messages and the caller's [count][n] sender bitmap in; the bitmap with the
     decoded READYs OR-ed in, each instance's ECHO / READY counts and its
     RBC_QUORUM_* flags out, in one submission.  Keeps no state between calls."""
+    _create, _destroy = "rbc_wire_quorum_create", "rbc_wire_quorum_destroy"
 
     def __init__(self, ctx: Context, max_count: int, max_msgs: int, max_ring_bytes: int):
         _lib.require_wire_ready()
-        p = c_void_p()
-        check(lib.rbc_wire_quorum_create(ctx._p, max_count, max_msgs, max_ring_bytes, byref(p)),
-              "rbc_wire_quorum_create")
-        self._p, self.ctx = p, ctx
-
-    def close(self) -> None:
-        if getattr(self, "_p", None):
-            lib.rbc_wire_quorum_destroy(self._p)
-            self._p = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+        super().__init__(ctx, max_count, max_msgs, max_ring_bytes)
 
     def quorum(self, ready: np.ndarray, **kw) -> dict:
         return self.submit(ready, **kw).wait()
@@ -1031,20 +1015,8 @@ class WireQuorum:
                                   _ptr(ix), p(rt), p(va), p(st), self_id, _ptr(ready), _ptr(out["verdict"]),
                                   _ptr(out["echo_counts"]), _ptr(out["ready_counts"]), _ptr(out["flags"]), byref(t)),
               "rbc_wire_quorum")
-        wq = self
-
-        class _Q(HostTicket):
-            def done(self_) -> bool:
-                d = c_int(0)
-                check(lib.rbc_wire_quorum_poll(wq._p, self_.ticket, byref(d)), "rbc_wire_quorum_poll")
-                return bool(d.value)
-
-            def wait(self_) -> dict:
-                if self_._keep is not None:
-                    check(lib.rbc_wire_quorum_wait(wq._p, self_.ticket), "rbc_wire_quorum_wait")
-                    self_._keep = None
-                return {k: v[:msgs] if k == "verdict" else v[:count] for k, v in out.items()}
-        return _Q(self.ctx, t.value, None, keep=(ring, o, ln, it, ix, rt, va, st, out))
+        return _WireTicket(self, "rbc_wire_quorum_poll", "rbc_wire_quorum_wait", t.value, out, msgs, count,
+                           ("verdict",), keep=(ring, o, ln, it, ix, rt, va, st, out))
 
 
 class Encoder:

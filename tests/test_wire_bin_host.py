@@ -14,22 +14,16 @@
 import json
 import os
 import re
-import shutil
-import subprocess
 
 import numpy as np
 import pytest
 
 import wire_bin as wb
+from san_program import build_and_run
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CPP = os.path.join(ROOT, "tests", "cpp")
 CSRC = os.path.join(ROOT, "cleisthenes_amd", "csrc")
 GOLDEN = os.path.join(ROOT, "tests", "golden", "wire_bin_v1.json")
-SAN = ["-std=c++17", "-O1", "-g", "-fno-omit-frame-pointer", "-fsanitize=address,undefined",
-       "-fno-sanitize-recover=all", "-Wall"]
-ENV = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:halt_on_error=1",
-           UBSAN_OPTIONS="print_stacktrace=1:halt_on_error=1")
 NEW = ("rbc_bin_encode_val", "rbc_bin_decode_val", "rbc_payload_decode_val", "rbc_val_message_size_codec",
        "rbc_ctx_set_wire_codec", "rbc_ctx_wire_codec", "rbc_node_set_wire_codec")
 
@@ -115,31 +109,10 @@ def test_val_message_size_codec_is_the_length_of_the_restated_message():
 
 
 def test_wire_bin_host_path_under_asan_ubsan(tmp_path):
-    if not shutil.which("g++"):
-        pytest.skip("g++ not available")
-    for h in ("hip/hip_runtime_api.h", "rccl/rccl.h"):  # types only: hip_stub links
-        if not os.path.exists(os.path.join("/opt/rocm/include", h)):
-            pytest.skip(f"/opt/rocm/include/{h} not available")
-    exe = str(tmp_path / "wire_bin_fuzz")
-    srcs = [os.path.join(CPP, f) for f in ("wire_bin_fuzz.cpp", "wire_bin_stub.cpp", "hip_stub.cpp")]
-    srcs += [os.path.join(CSRC, f) for f in ("capi.cpp", "batcher.cpp", "rbc_node.cpp", "wire_rx.cpp",
-                                             "wire_receive.cpp")]
-    objs, procs = [], []
-    for s in srcs:  # one compiler per file: capi.cpp alone takes most of the time
-        objs.append(str(tmp_path / (os.path.basename(s) + ".o")))
-        procs.append(subprocess.Popen(["g++", *SAN, "-D__HIP_PLATFORM_AMD__", "-I/opt/rocm/include", "-c", s, "-o",
-                                       objs[-1]], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True))
-    for s, p in zip(srcs, procs):
-        out, _ = p.communicate()
-        assert p.returncode == 0, f"{s}:\n{out}"
-    r = subprocess.run(["g++", *SAN, "-o", exe, *objs, "-ldl", "-lpthread"], capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr
-    r = subprocess.run([exe], capture_output=True, text=True, timeout=300, env=ENV)
-    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
-    for bad in ("AddressSanitizer", "runtime error", "FAIL"):
-        assert bad not in r.stderr, r.stderr[-4000:]
-    words = r.stdout.split()
-    assert words[0] == "ok" and int(words[1]) > 100000, r.stdout  # the whole corpus ran
+    stdout = build_and_run(tmp_path, "wire_bin_fuzz", cpp=("wire_bin_fuzz.cpp", "wire_bin_stub.cpp", "hip_stub.cpp"),
+                           csrc=("capi.cpp", "batcher.cpp", "rbc_node.cpp", "wire_rx.cpp", "wire_receive.cpp"))
+    words = stdout.split()
+    assert words[0] == "ok" and int(words[1]) > 100000, stdout  # the whole corpus ran
 
 
 def test_header_announces_the_binary_codec_and_the_library_exports_it():

@@ -15,49 +15,22 @@ table over every (E, R, status, own bit) at (4, 1), (7, 2) and (4, 0).
 import json
 import os
 import re
-import shutil
-import subprocess
 
-import pytest
+from san_program import build_and_run
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CPP = os.path.join(ROOT, "tests", "cpp")
 CSRC = os.path.join(ROOT, "cleisthenes_amd", "csrc")
-SAN = ["-std=c++17", "-O1", "-g", "-fno-omit-frame-pointer", "-fsanitize=address,undefined",
-       "-fno-sanitize-recover=all", "-Wall"]
-ENV = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:halt_on_error=1",
-           UBSAN_OPTIONS="print_stacktrace=1:halt_on_error=1")
 NEW = ("rbc_dev_unmarshal_ready", "rbc_dev_quorum", "rbc_wire_quorum_create", "rbc_wire_quorum_destroy",
        "rbc_wire_quorum", "rbc_wire_quorum_wait", "rbc_wire_quorum_poll")
 
 
 def test_wire_ready_host_path_under_asan_ubsan(tmp_path):
-    if not shutil.which("g++"):
-        pytest.skip("g++ not available")
-    for h in ("hip/hip_runtime_api.h", "rccl/rccl.h"):  # types only: hip_stub links
-        if not os.path.exists(os.path.join("/opt/rocm/include", h)):
-            pytest.skip(f"/opt/rocm/include/{h} not available")
-    exe = str(tmp_path / "wire_ready_fuzz")
-    srcs = [os.path.join(CPP, f) for f in ("wire_ready_fuzz.cpp", "wire_ready_stub.cpp", "hip_stub.cpp")]
-    srcs += [os.path.join(CSRC, f) for f in ("capi.cpp", "batcher.cpp", "rbc_node.cpp", "wire_ready.cpp")]
-    objs = []
-    procs = []
-    for s in srcs:  # one compiler per file: capi.cpp alone takes most of the time
-        objs.append(str(tmp_path / (os.path.basename(s) + ".o")))
-        procs.append(subprocess.Popen(["g++", *SAN, "-D__HIP_PLATFORM_AMD__", "-I/opt/rocm/include", "-c", s, "-o",
-                                       objs[-1]], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True))
-    for s, p in zip(srcs, procs):
-        out, _ = p.communicate()
-        assert p.returncode == 0, f"{s}:\n{out}"
-    r = subprocess.run(["g++", *SAN, "-o", exe, *objs, "-ldl", "-lpthread"], capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr
-    r = subprocess.run([exe], capture_output=True, text=True, timeout=300, env=ENV)
-    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
-    for bad in ("AddressSanitizer", "runtime error", "FAIL"):
-        assert bad not in r.stderr, r.stderr[-4000:]
-    words = r.stdout.split()
+    stdout = build_and_run(tmp_path, "wire_ready_fuzz",
+                           cpp=("wire_ready_fuzz.cpp", "wire_ready_stub.cpp", "hip_stub.cpp"),
+                           csrc=("capi.cpp", "batcher.cpp", "rbc_node.cpp", "wire_ready.cpp"))
+    words = stdout.split()
     # the whole corpus (65 bytes x 255 values and the rest) and the three quorum tables ran
-    assert words[0] == "ok" and int(words[1]) > 16000 and int(words[3]) > 3000, r.stdout
+    assert words[0] == "ok" and int(words[1]) > 16000 and int(words[3]) > 3000, stdout
 
 
 def test_header_announces_the_ready_path_and_the_library_exports_it():

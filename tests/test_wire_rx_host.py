@@ -10,38 +10,18 @@ mutation corpus of tests/test_gpu_wire_rx.py against the host decoder, and that
 buffers sized exactly to the contract are never overrun.
 """
 import os
-import shutil
-import subprocess
 
-import pytest
+from san_program import build_and_run
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CPP = os.path.join(ROOT, "tests", "cpp")
 CSRC = os.path.join(ROOT, "cleisthenes_amd", "csrc")
-SAN = ["-std=c++17", "-O1", "-g", "-fno-omit-frame-pointer", "-fsanitize=address,undefined",
-       "-fno-sanitize-recover=all", "-Wall"]
-ENV = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:halt_on_error=1",
-           UBSAN_OPTIONS="print_stacktrace=1:halt_on_error=1")
 
 
 def test_wire_rx_host_path_under_asan_ubsan(tmp_path):
-    if not shutil.which("g++"):
-        pytest.skip("g++ not available")
-    for h in ("hip/hip_runtime_api.h", "rccl/rccl.h"):  # types only: hip_stub links
-        if not os.path.exists(os.path.join("/opt/rocm/include", h)):
-            pytest.skip(f"/opt/rocm/include/{h} not available")
-    exe = str(tmp_path / "wire_rx_fuzz")
-    srcs = [os.path.join(CPP, f) for f in ("wire_rx_fuzz.cpp", "wire_rx_stub.cpp", "hip_stub.cpp")]
-    srcs += [os.path.join(CSRC, f) for f in ("capi.cpp", "batcher.cpp", "rbc_node.cpp", "wire_rx.cpp")]
-    r = subprocess.run(["g++", *SAN, "-D__HIP_PLATFORM_AMD__", "-I/opt/rocm/include", "-o", exe, *srcs, "-ldl",
-                        "-lpthread"], capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr
-    r = subprocess.run([exe], capture_output=True, text=True, timeout=300, env=ENV)
-    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
-    for bad in ("AddressSanitizer", "runtime error", "FAIL"):
-        assert bad not in r.stderr, r.stderr[-4000:]
-    words = r.stdout.split()
-    assert words[0] == "ok" and int(words[1]) > 3000, r.stdout  # the whole corpus ran
+    stdout = build_and_run(tmp_path, "wire_rx_fuzz", cpp=("wire_rx_fuzz.cpp", "wire_rx_stub.cpp", "hip_stub.cpp"),
+                           csrc=("capi.cpp", "batcher.cpp", "rbc_node.cpp", "wire_rx.cpp"))
+    words = stdout.split()
+    assert words[0] == "ok" and int(words[1]) > 3000, stdout  # the whole corpus ran
 
 
 def test_header_announces_the_wire_receive_path_and_the_library_exports_it():
