@@ -157,7 +157,14 @@ int rbc_device_mem_info(int device, size_t *free_bytes, size_t *total_bytes);
  * per instance (device uint32 array) or, when that pointer is NULL, uniform.
  * shard_pitch % 64 == 0 and >= S_i; value rows must be readable for
  * round_up(k*S_i, 16) + 16 bytes (value_pitch >= that; contents past B_i are
- * ignored -- the Split zero pad is produced by masking).                    */
+ * ignored -- the Split zero pad is produced by masking).
+ * Bytes [S_i, shard_pitch) of a received row are ignored on input by
+ * rbc_dev_verify, rbc_dev_interpolate and rbc_dev_receive_step (they need not
+ * be zero).  After interpolate or the receive step every regenerated row (an
+ * absent position, or an ECHO that did not verify) is zero there.  The pad of
+ * a received row is unspecified after the call.
+ * `count` may exceed 65535 on either codec (the FFT launch carries the
+ * instance in gridDim.y, which the runtime accepts; tested at 65547).       */
 
 /* shard(): Split + Encode.  values [count][value_pitch] (B_i bytes used) ->
  * shards [count][n][shard_pitch] (data rows 0..k-1 + parity rows k..n-1;
