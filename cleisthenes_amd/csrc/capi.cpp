@@ -26,6 +26,7 @@
 #include "../../include/rbc_protocol.h"
 #include "gf_host.h"
 #include "kernels.h"
+#include "wire_session.h"
 
 namespace {
 
@@ -131,7 +132,6 @@ struct Slot {
     DevBuf h_in{nullptr, 0, true}, h_out{nullptr, 0, true};
     Ws ws;
     hipStream_t stream = nullptr;
-    hipStream_t dstream = nullptr;  // RBC_D2H_STREAM: the submission's D2H copies, gated on kdone
     hipEvent_t done = nullptr;
     // recorded after the submission's kernels, before its deferred D2H: a
     // waiter enqueues the D2H only once the kernels are done, so the copy
@@ -154,11 +154,9 @@ struct Slot {
             b->release();
         ws.release();
         if (stream) (void)hipStreamDestroy(stream);
-        if (dstream) (void)hipStreamDestroy(dstream);
         if (done) (void)hipEventDestroy(done);
         if (kdone) (void)hipEventDestroy(kdone);
         stream = nullptr;
-        dstream = nullptr;
         done = nullptr;
         kdone = nullptr;
     }
@@ -166,9 +164,6 @@ struct Slot {
 
 // host-API submissions in flight per context: the batcher keeps 4 launches
 // in flight (tools/batcher_bench.cpp), and the box has 4 hardware queues
-#ifndef RBC_D2H_STREAM
-#define RBC_D2H_STREAM 0
-#endif
 #ifndef RBC_HOST_SLOTS
 #define RBC_HOST_SLOTS 4
 #endif
@@ -199,10 +194,9 @@ struct rbc_ctx {
     std::mutex mu;
     hipStream_t stream = nullptr;  // Encoder-mirror stream (created on first use)
     Ws ws;                         // interpolate workspace of the device API
-    // host-API staging
-    DevBuf d_values, d_shards, d_leaves, d_roots, d_branches, d_valid, d_status, d_digests, d_lens, d_slens,
-        d_idx, d_present;
-    DevBuf h_stage{nullptr, 0, true}, h_small{nullptr, 0, true};
+    // staging of the single-call drop-ins (host_reconstruct, the rbc_rs mirror)
+    DevBuf d_values, d_shards, d_valid, d_status;
+    DevBuf h_stage{nullptr, 0, true};
     uint64_t next_ticket = 1;
     std::vector<std::unique_ptr<Slot>> slots;        // host-API pipeline
     std::unordered_map<uint64_t, int> retired;       // completed tickets not yet waited on
@@ -269,37 +263,54 @@ hipStream_t aux_stream(Ws &w) {
 }
 
 // ------------------------------------------------------------ stage bodies
+// Where a batch's shard rows live on the device: one buffer [count][n][pitch],
+// or (split, rbc_dev_shard_commit_parity) the k data rows in rows
+// [count][k][pitch] and the p parity rows in the dense arena parity
+// [count][p][pitch].
+struct Rows {
+    uint8_t *rows;
+    uint32_t pitch;
+    bool split = false;
+    uint8_t *parity = nullptr;
+    // a buffer the form needs is NULL
+    bool missing(const rbc_ctx *c) const { return !rows || (split && c->p > 0 && !parity); }
+};
+
 int stage_encode(rbc_ctx *c, hipStream_t st, int count, const uint8_t *values, uint64_t value_pitch,
-                 const uint32_t *value_lens, uint32_t uniform_value_len, uint8_t *shards, uint32_t shard_pitch) {
-    if (count < 0 || (count > 0 && (!values || !shards))) return RBC_ERR_INVALID_ARG;
-    if (shard_pitch == 0 || shard_pitch % kAlign) return RBC_ERR_INVALID_ARG;
+                 const uint32_t *value_lens, uint32_t uniform_value_len, const Rows &out) {
+    if (count < 0 || (count > 0 && (!values || out.missing(c)))) return RBC_ERR_INVALID_ARG;
+    if (out.pitch == 0 || out.pitch % kAlign) return RBC_ERR_INVALID_ARG;
     if (!value_lens) {
         if (uniform_value_len == 0) return RBC_ERR_SHORT_DATA;
         const size_t S = (uniform_value_len + c->k - 1) / c->k;
-        if (S > shard_pitch || value_pitch < round_up((size_t)c->k * S, 16) + 16) return RBC_ERR_INVALID_ARG;
+        if (S > out.pitch || value_pitch < round_up((size_t)c->k * S, 16) + 16) return RBC_ERR_INVALID_ARG;
     }
-    if (value_pitch > 0x7fffffffULL || (uint64_t)c->n * shard_pitch > 0x7fffffffULL) return RBC_ERR_INVALID_ARG;
+    if (value_pitch > 0x7fffffffULL || (uint64_t)c->n * out.pitch > 0x7fffffffULL) return RBC_ERR_INVALID_ARG;
     if (count == 0) return RBC_OK;
+    const uint64_t inst_pitch = (uint64_t)(out.split ? c->k : c->n) * out.pitch;
+    const uint64_t parity_inst_pitch = out.split ? (uint64_t)c->p * out.pitch : 0;
     if (c->fft) {
         FftArgs a{};
         a.count = count;
         a.n = c->n;
         a.k = c->k;
-        a.mode = GF_MODE_ENCODE;
+        a.mode = out.split ? GF_MODE_ENCODE_PARITY : GF_MODE_ENCODE;
         a.values = values;
         a.value_pitch = (uint32_t)value_pitch;
-        a.shards = shards;
-        a.inst_pitch = (uint64_t)c->n * shard_pitch;
-        a.row_pitch = shard_pitch;
+        a.shards = out.rows;
+        a.inst_pitch = inst_pitch;
+        a.row_pitch = out.pitch;
         a.lens = value_lens;
         a.uniform_len = uniform_value_len;
         a.prio = c->tx_prio;
+        a.parity = out.parity;
+        a.parity_inst_pitch = parity_inst_pitch;
         RBC_HIP(rbc_launch_rs_fft(a, st));
         return RBC_OK;
     }
     GfArgs g{};
     g.count = count;
-    g.tiles = (int)((shard_pitch + 4095) / 4096);
+    g.tiles = (int)((out.pitch + 4095) / 4096);
     g.R = c->p;
     g.K = c->k;
     g.rc = rbc_gf_pick_rc(c->p > 0 ? c->p : 1, kGfRcMax);
@@ -307,31 +318,36 @@ int stage_encode(rbc_ctx *c, hipStream_t st, int count, const uint8_t *values, u
     g.in = values;
     g.in_inst_pitch = value_pitch;
     g.in_inst_bytes = (uint32_t)value_pitch;
-    g.out = shards;
-    g.out_inst_pitch = (uint64_t)c->n * shard_pitch;
-    g.out_row_pitch = shard_pitch;
-    g.copy = shards;
+    g.out = out.rows;  // split: not written, the R rows go to the arena (p == 0: no output rows at all)
+    g.out_inst_pitch = inst_pitch;
+    g.out_row_pitch = out.pitch;
+    g.copy = out.rows;
     g.lens = value_lens;
     g.uniform_len = uniform_value_len;
     g.coef = c->d_M + (size_t)c->k * c->k;
     g.coef_inst_stride = 0;
     g.prio = c->tx_prio;
+    g.parity = c->p > 0 ? out.parity : nullptr;
+    g.parity_inst_pitch = parity_inst_pitch;
     RBC_HIP(rbc_launch_gf_rows(g, st));
     return RBC_OK;
 }
 
-int stage_leaves(rbc_ctx *c, hipStream_t st, int count, const uint8_t *shards, uint32_t shard_pitch,
-                 const uint32_t *shard_lens, uint32_t uniform_shard_len, uint8_t *leaves) {
-    if (count < 0 || (count > 0 && (!shards || !leaves))) return RBC_ERR_INVALID_ARG;
-    if (shard_pitch % kAlign || (!shard_lens && (uniform_shard_len == 0 || uniform_shard_len > shard_pitch)))
+// leaves [count][n][32] of the rows: one launch of the row hashing over the n
+// rows of one buffer, or (split) one over the k data rows and one over the p
+// arena rows -- each over a dense [count][rows][pitch] buffer.
+int stage_leaves(rbc_ctx *c, hipStream_t st, int count, const Rows &in, const uint32_t *shard_lens,
+                 uint32_t uniform_shard_len, uint8_t *leaves) {
+    if (count < 0 || (count > 0 && (in.missing(c) || !leaves))) return RBC_ERR_INVALID_ARG;
+    if (in.pitch % kAlign || (!shard_lens && (uniform_shard_len == 0 || uniform_shard_len > in.pitch)))
         return RBC_ERR_INVALID_ARG;
     if (count == 0) return RBC_OK;
     ShaArgs a{};
     a.count = count;
-    a.rows_per_inst = c->n;
-    a.rows = shards;
-    a.inst_pitch = (uint64_t)c->n * shard_pitch;
-    a.row_pitch = shard_pitch;
+    a.rows_per_inst = in.split ? c->k : c->n;
+    a.rows = in.rows;
+    a.inst_pitch = (uint64_t)a.rows_per_inst * in.pitch;
+    a.row_pitch = in.pitch;
     a.lens = shard_lens;
     a.uniform_len = uniform_shard_len;
     a.leaves = leaves;
@@ -340,95 +356,10 @@ int stage_leaves(rbc_ctx *c, hipStream_t st, int count, const uint8_t *shards, u
     a.depth = c->depth;
     a.prio = c->tx_prio;
     RBC_HIP(rbc_launch_sha_rows(a, false, st));
-    return RBC_OK;
-}
-
-// stage_encode with two outputs (rbc_dev_shard_commit_parity): the k data rows
-// to data_rows [count][k][pitch], the p parity rows to the dense arena parity
-// [count][p][pitch].  Same argument rules as stage_encode.
-int stage_encode_parity(rbc_ctx *c, hipStream_t st, int count, const uint8_t *values, uint64_t value_pitch,
-                        const uint32_t *value_lens, uint32_t uniform_value_len, uint8_t *data_rows, uint8_t *parity,
-                        uint32_t pitch) {
-    if (count < 0 || (count > 0 && (!values || !data_rows || (c->p > 0 && !parity)))) return RBC_ERR_INVALID_ARG;
-    if (pitch == 0 || pitch % kAlign) return RBC_ERR_INVALID_ARG;
-    if (!value_lens) {
-        if (uniform_value_len == 0) return RBC_ERR_SHORT_DATA;
-        const size_t S = (uniform_value_len + c->k - 1) / c->k;
-        if (S > pitch || value_pitch < round_up((size_t)c->k * S, 16) + 16) return RBC_ERR_INVALID_ARG;
-    }
-    if (value_pitch > 0x7fffffffULL || (uint64_t)c->n * pitch > 0x7fffffffULL) return RBC_ERR_INVALID_ARG;
-    if (count == 0) return RBC_OK;
-    if (c->fft) {
-        FftArgs a{};
-        a.count = count;
-        a.n = c->n;
-        a.k = c->k;
-        a.mode = GF_MODE_ENCODE_PARITY;
-        a.values = values;
-        a.value_pitch = (uint32_t)value_pitch;
-        a.shards = data_rows;
-        a.inst_pitch = (uint64_t)c->k * pitch;
-        a.row_pitch = pitch;
-        a.lens = value_lens;
-        a.uniform_len = uniform_value_len;
-        a.prio = c->tx_prio;
-        a.parity = parity;
-        a.parity_inst_pitch = (uint64_t)c->p * pitch;
-        RBC_HIP(rbc_launch_rs_fft(a, st));
-        return RBC_OK;
-    }
-    GfArgs g{};
-    g.count = count;
-    g.tiles = (int)((pitch + 4095) / 4096);
-    g.R = c->p;
-    g.K = c->k;
-    g.rc = rbc_gf_pick_rc(c->p > 0 ? c->p : 1, kGfRcMax);
-    g.mode = GF_MODE_ENCODE;
-    g.in = values;
-    g.in_inst_pitch = value_pitch;
-    g.in_inst_bytes = (uint32_t)value_pitch;
-    g.out = data_rows;  // not written: R rows go to the arena (p == 0: no output rows at all)
-    g.out_inst_pitch = (uint64_t)c->k * pitch;
-    g.out_row_pitch = pitch;
-    g.copy = data_rows;
-    g.lens = value_lens;
-    g.uniform_len = uniform_value_len;
-    g.coef = c->d_M + (size_t)c->k * c->k;
-    g.coef_inst_stride = 0;
-    g.prio = c->tx_prio;
-    g.parity = c->p > 0 ? parity : nullptr;
-    g.parity_inst_pitch = (uint64_t)c->p * pitch;
-    RBC_HIP(rbc_launch_gf_rows(g, st));
-    return RBC_OK;
-}
-
-// stage_leaves over the two buffers of stage_encode_parity: leaves [count][n][32]
-// as ever, slots 0..k-1 from the data rows and k..n-1 from the arena -- two
-// launches of the row hashing, each over a dense [count][rows][pitch] buffer.
-int stage_leaves_parity(rbc_ctx *c, hipStream_t st, int count, const uint8_t *data_rows, const uint8_t *parity,
-                        uint32_t pitch, const uint32_t *shard_lens, uint32_t uniform_shard_len, uint8_t *leaves) {
-    if (count < 0 || (count > 0 && (!data_rows || !leaves || (c->p > 0 && !parity)))) return RBC_ERR_INVALID_ARG;
-    if (pitch % kAlign || (!shard_lens && (uniform_shard_len == 0 || uniform_shard_len > pitch)))
-        return RBC_ERR_INVALID_ARG;
-    if (count == 0) return RBC_OK;
-    ShaArgs a{};
-    a.count = count;
-    a.row_pitch = pitch;
-    a.lens = shard_lens;
-    a.uniform_len = uniform_shard_len;
-    a.leaves_inst_pitch = (uint64_t)c->n * 32;
-    a.n = c->n;
-    a.depth = c->depth;
-    a.prio = c->tx_prio;
-    a.rows_per_inst = c->k;
-    a.rows = data_rows;
-    a.inst_pitch = (uint64_t)c->k * pitch;
-    a.leaves = leaves;
-    RBC_HIP(rbc_launch_sha_rows(a, false, st));
-    if (c->p > 0) {
+    if (in.split && c->p > 0) {
         a.rows_per_inst = c->p;
-        a.rows = parity;
-        a.inst_pitch = (uint64_t)c->p * pitch;
+        a.rows = in.parity;
+        a.inst_pitch = (uint64_t)c->p * in.pitch;
         a.leaves = leaves + (size_t)32 * c->k;  // slot s of this launch is leaf k + s
         RBC_HIP(rbc_launch_sha_rows(a, false, st));
     }
@@ -453,6 +384,18 @@ int stage_merkle_build(rbc_ctx *c, hipStream_t st, int count, const uint8_t *lea
     m.prio = c->tx_prio;
     RBC_HIP(rbc_launch_merkle(m, false, st));
     return RBC_OK;
+}
+
+// encode -> leaves -> tree: the shard commit of every entry point, device or host
+int commit_stages(rbc_ctx *c, hipStream_t st, int count, const uint8_t *values, uint64_t value_pitch,
+                  const uint32_t *value_lens, uint32_t uniform_value_len, const Rows &rows,
+                  const uint32_t *shard_lens, uint8_t *leaves, uint8_t *roots, uint8_t *branches) {
+    int rc = stage_encode(c, st, count, values, value_pitch, value_lens, uniform_value_len, rows);
+    if (rc) return rc;
+    const uint32_t uS = value_lens ? 0u : (uniform_value_len + c->k - 1) / c->k;
+    rc = stage_leaves(c, st, count, rows, shard_lens, uS, leaves);
+    if (rc) return rc;
+    return stage_merkle_build(c, st, count, leaves, roots, branches);
 }
 
 // ECHO verify's form: leaf hashes + the shared-path verify
@@ -1201,10 +1144,7 @@ void rbc_ctx_destroy(rbc_ctx *c) {
         sl->release();
     }
     c->ws.release();
-    for (DevBuf *b : {&c->d_values, &c->d_shards, &c->d_leaves,
-                      &c->d_roots, &c->d_branches, &c->d_valid, &c->d_status, &c->d_digests, &c->d_lens,
-                      &c->d_slens, &c->d_idx, &c->d_present, &c->h_stage, &c->h_small, &c->d_pack})
-        b->release();
+    for (DevBuf *b : {&c->d_values, &c->d_shards, &c->d_valid, &c->d_status, &c->h_stage, &c->d_pack}) b->release();
     if (c->d_M) (void)hipFree(c->d_M);
     if (c->stream) (void)hipStreamDestroy(c->stream);
     delete c;
@@ -1353,15 +1293,16 @@ int rbc_dev_encode(rbc_ctx *c, void *stream, int count, const uint8_t *values, u
                    const uint32_t *value_lens, uint32_t uniform_value_len, uint8_t *shards, uint32_t shard_pitch) {
     if (!c) return RBC_ERR_INVALID_ARG;
     RBC_HIP(hipSetDevice(c->device));
-    return stage_encode(c, as_stream(stream), count, values, value_pitch, value_lens, uniform_value_len, shards,
-                        shard_pitch);
+    return stage_encode(c, as_stream(stream), count, values, value_pitch, value_lens, uniform_value_len,
+                        {shards, shard_pitch});
 }
 
 int rbc_dev_leaves(rbc_ctx *c, void *stream, int count, const uint8_t *shards, uint32_t shard_pitch,
                    const uint32_t *shard_lens, uint32_t uniform_shard_len, uint8_t *leaves) {
     if (!c) return RBC_ERR_INVALID_ARG;
     RBC_HIP(hipSetDevice(c->device));
-    return stage_leaves(c, as_stream(stream), count, shards, shard_pitch, shard_lens, uniform_shard_len, leaves);
+    return stage_leaves(c, as_stream(stream), count, {const_cast<uint8_t *>(shards), shard_pitch}, shard_lens,
+                        uniform_shard_len, leaves);
 }
 
 int rbc_dev_merkle_build(rbc_ctx *c, void *stream, int count, const uint8_t *leaves, uint8_t *roots,
@@ -1378,13 +1319,8 @@ int rbc_dev_shard_commit(rbc_ctx *c, void *stream, int count, const uint8_t *val
     if (!c) return RBC_ERR_INVALID_ARG;
     if (value_lens && !shard_lens) return RBC_ERR_INVALID_ARG;
     RBC_HIP(hipSetDevice(c->device));
-    hipStream_t st = as_stream(stream);
-    int rc = stage_encode(c, st, count, values, value_pitch, value_lens, uniform_value_len, shards, shard_pitch);
-    if (rc) return rc;
-    const uint32_t uS = value_lens ? 0u : (uniform_value_len + c->k - 1) / c->k;
-    rc = stage_leaves(c, st, count, shards, shard_pitch, shard_lens, uS, leaves);
-    if (rc) return rc;
-    return stage_merkle_build(c, st, count, leaves, roots, branches);
+    return commit_stages(c, as_stream(stream), count, values, value_pitch, value_lens, uniform_value_len,
+                         {shards, shard_pitch}, shard_lens, leaves, roots, branches);
 }
 
 int rbc_dev_shard_commit_parity(rbc_ctx *c, void *stream, int count, const uint8_t *values, uint64_t value_pitch,
@@ -1395,14 +1331,8 @@ int rbc_dev_shard_commit_parity(rbc_ctx *c, void *stream, int count, const uint8
     if (value_lens && !shard_lens) return RBC_ERR_INVALID_ARG;
     if (count > 0 && (!leaves || !roots)) return RBC_ERR_INVALID_ARG;  // before the first launch
     RBC_HIP(hipSetDevice(c->device));
-    hipStream_t st = as_stream(stream);
-    int rc = stage_encode_parity(c, st, count, values, value_pitch, value_lens, uniform_value_len, data_rows, parity,
-                                 row_pitch);
-    if (rc) return rc;
-    const uint32_t uS = value_lens ? 0u : (uniform_value_len + c->k - 1) / c->k;
-    rc = stage_leaves_parity(c, st, count, data_rows, parity, row_pitch, shard_lens, uS, leaves);
-    if (rc) return rc;
-    return stage_merkle_build(c, st, count, leaves, roots, branches);
+    return commit_stages(c, as_stream(stream), count, values, value_pitch, value_lens, uniform_value_len,
+                         {data_rows, row_pitch, true, parity}, shard_lens, leaves, roots, branches);
 }
 
 int rbc_dev_verify(rbc_ctx *c, void *stream, int count, const uint8_t *shards, uint32_t shard_pitch,
@@ -1550,7 +1480,6 @@ Slot *acquire_slot(rbc_ctx *c) {
     if ((int)c->slots.size() < kHostSlots) {
         auto sl = std::make_unique<Slot>();
         if (hipStreamCreateWithFlags(&sl->stream, hipStreamNonBlocking) != hipSuccess ||
-            (RBC_D2H_STREAM && hipStreamCreateWithFlags(&sl->dstream, hipStreamNonBlocking) != hipSuccess) ||
             // blocking-sync events: a host-API waiter (the batcher's completer, a
             // goroutine's cgo call) sleeps instead of spinning a core the
             // submitting threads need for their staging copies
@@ -1584,20 +1513,7 @@ int submit(rbc_ctx *c, Slot &s, uint64_t *ticket, std::function<int()> finish,
 #ifndef RBC_DEFER_D2H
 #define RBC_DEFER_D2H 1
 #endif
-    if (RBC_D2H_STREAM && d2h) {
-        // the D2H copies go on the slot's own copy stream at once, behind an
-        // event wait on its kernels: nothing waits in front of the next
-        // submission's H2D on the compute stream, and no host call has to
-        // enqueue them later
-        const int rc = hipEventRecord(s.kdone, s.stream) != hipSuccess ||
-                               hipStreamWaitEvent(s.dstream, s.kdone, 0) != hipSuccess
-                           ? RBC_ERR_DEVICE
-                           : d2h(s.dstream);
-        if (rc || hipEventRecord(s.done, s.dstream) != hipSuccess) {
-            s.finish = nullptr;
-            return rc ? rc : RBC_ERR_DEVICE;
-        }
-    } else if (RBC_DEFER_D2H && d2h && ticket) {
+    if (RBC_DEFER_D2H && d2h && ticket) {
         if (hipEventRecord(s.kdone, s.stream) != hipSuccess) {
             s.finish = nullptr;
             return RBC_ERR_DEVICE;
@@ -1617,77 +1533,90 @@ int submit(rbc_ctx *c, Slot &s, uint64_t *ticket, std::function<int()> finish,
     return RBC_OK;
 }
 
-}  // namespace
-}  // extern "C++"
+// The prologue of every submission: the context's lock, its device, a free slot
+// (NULL: device error).
+Slot *open_slot(rbc_ctx *c, std::unique_lock<std::mutex> &lk) {
+    lk = std::unique_lock<std::mutex>(c->mu);
+    return hipSetDevice(c->device) == hipSuccess ? acquire_slot(c) : nullptr;
+}
 
 // Caller memory that is already pinned (rbc_host_alloc / hipHostMalloc /
 // hipHostRegister) is copied to and from directly: no staging memcpy.  A Go
 // batcher that keeps its request and result rings in rbc_host_alloc memory
 // gets the PCIe-only path.
-static bool host_pinned(const void *p, size_t bytes) {
+// Both ends of [p, p + bytes) pass `ok`: one attribute query each.
+template <class Pred>
+bool range_is(const void *p, size_t bytes, Pred ok) {
     if (!p) return false;
     for (const void *q : {p, (const void *)((const uint8_t *)p + (bytes ? bytes - 1 : 0))}) {
         hipPointerAttribute_t a;
-        if (hipPointerGetAttributes(&a, q) != hipSuccess) {
-            (void)hipGetLastError();
-            return false;
-        }
-        if (a.type != hipMemoryTypeHost) return false;
+        if (!wire::pointer_type(q, &a) || !ok(a, q)) return false;
     }
     return true;
 }
 
+bool host_pinned(const void *p, size_t bytes) {
+    return range_is(p, bytes, [](const hipPointerAttribute_t &a, const void *) { return a.type == hipMemoryTypeHost; });
+}
+
 // [p, p + bytes) readable by a kernel: device memory, or pinned host memory
-// mapped at the same address (both ends checked: one attribute query each)
-static bool device_readable(const void *p, size_t bytes) {
-    if (!p) return false;
-    for (const void *q : {p, (const void *)((const uint8_t *)p + (bytes ? bytes - 1 : 0))}) {
-        hipPointerAttribute_t a;
-        if (hipPointerGetAttributes(&a, q) != hipSuccess) {
-            (void)hipGetLastError();
-            return false;
-        }
-        if (a.type == hipMemoryTypeDevice) continue;
-        if (a.type == hipMemoryTypeHost && a.devicePointer == q) continue;
-        return false;
-    }
-    return true;
+// mapped at the same address
+bool device_readable(const void *p, size_t bytes) {
+    return range_is(p, bytes, [](const hipPointerAttribute_t &a, const void *q) {
+        return a.type == hipMemoryTypeDevice || (a.type == hipMemoryTypeHost && a.devicePointer == q);
+    });
 }
 
 // The device address of pinned caller memory when it is the host address itself
 // (hipHostMalloc / rbc_host_alloc under unified addressing), else NULL: a
 // kernel may then read it directly over PCIe.
-inline int n_of(const rbc_ctx *c) { return c->n; }
 #ifndef RBC_ZERO_COPY_READS
 #define RBC_ZERO_COPY_READS 1
 #endif
-static const uint8_t *host_zero_copy(const void *p, size_t bytes) {
-    if (!RBC_ZERO_COPY_READS || !host_pinned(p, bytes)) return nullptr;
+const uint8_t *host_zero_copy(const void *p, size_t bytes) {
     hipPointerAttribute_t a;
-    if (hipPointerGetAttributes(&a, p) != hipSuccess) {
-        (void)hipGetLastError();
-        return nullptr;
-    }
+    if (!RBC_ZERO_COPY_READS || !host_pinned(p, bytes) || !wire::pointer_type(p, &a)) return nullptr;
     return a.devicePointer == p ? static_cast<const uint8_t *>(p) : nullptr;
 }
 
 // Every value in pinned memory?  *zc: also each readable zero-copy at its own
 // address (two attribute queries per value, as host_pinned).
-static bool values_pinned(const uint8_t *const *values, const size_t *lens, int count, bool *zc) {
+bool values_pinned(const uint8_t *const *values, const size_t *lens, int count, bool *zc) {
     *zc = RBC_ZERO_COPY_READS != 0;
     for (int i = 0; i < count; ++i) {
         for (int e = 0; e < 2; ++e) {
             const void *q = values[i] + (e ? lens[i] - 1 : 0);
             hipPointerAttribute_t a;
-            if (hipPointerGetAttributes(&a, q) != hipSuccess) {
-                (void)hipGetLastError();
-                return false;
-            }
-            if (a.type != hipMemoryTypeHost) return false;
+            if (!wire::pointer_type(q, &a) || a.type != hipMemoryTypeHost) return false;
             if (!e && a.devicePointer != q) *zc = false;
         }
     }
     return true;
+}
+
+// ---- what rbc_shard_commit, _parity and _val share
+
+// Smax: the longest shard of the batch; vpitch: its device value row
+struct ValueScan {
+    size_t Smax = 0, vpitch = 0;
+};
+
+// The argument scan of a commit.  `outs`: the entry point's own outputs are
+// there.  count == 0 completes here (*ticket = 0): the caller returns on
+// `rc || count == 0`.
+int scan_values(const rbc_ctx *c, int count, const uint8_t *const *values, const size_t *value_lens, bool outs,
+                uint64_t *ticket, ValueScan *v) {
+    if (!c || count < 0 || (count > 0 && (!values || !value_lens || !outs))) return RBC_ERR_INVALID_ARG;
+    if (count == 0) { if (ticket) *ticket = 0; return RBC_OK; }
+    for (int i = 0; i < count; ++i) {
+        if (value_lens[i] == 0) return RBC_ERR_SHORT_DATA;  // Split: len(data) == 0
+        if (!values[i]) return RBC_ERR_INVALID_ARG;
+        v->Smax = std::max(v->Smax, (value_lens[i] + c->k - 1) / c->k);
+    }
+    v->vpitch = round_up((size_t)c->k * v->Smax + 32, kAlign);
+    // a caller's own row pitch (RowsOut::flat) is bounded where it is taken
+    if (v->vpitch > 0x7fffffffULL || (size_t)c->n * round_up(v->Smax, 128) > 0x7fffffffULL) return RBC_ERR_INVALID_ARG;
+    return RBC_OK;
 }
 
 // The pinned values of a shard_commit submission into the device value rows:
@@ -1695,9 +1624,8 @@ static bool values_pinned(const uint8_t *const *values, const size_t *lens, int 
 // gather launch over their addresses (host time per DMA call dominated C4's
 // 16,384-value epoch).  `lens` ([2*count] u32, pinned staging) is uploaded
 // here when the gather needs it; `ptr_stage` has room for count addresses.
-static int upload_pinned_values(Slot &s, hipStream_t st, int count, const uint8_t *const *values,
-                                const size_t *value_lens, size_t vpitch, bool zc, uint32_t *lens,
-                                uint64_t *ptr_stage) {
+int upload_pinned_values(Slot &s, hipStream_t st, int count, const uint8_t *const *values, const size_t *value_lens,
+                         size_t vpitch, bool zc, uint32_t *lens, uint64_t *ptr_stage) {
     size_t total = 0;
     for (int i = 0; i < count; ++i) total += value_lens[i];
     if (zc && count >= 64 && total / count < ((size_t)256 << 10)) {
@@ -1715,215 +1643,190 @@ static int upload_pinned_values(Slot &s, hipStream_t st, int count, const uint8_
     return RBC_OK;
 }
 
-int rbc_shard_commit(rbc_ctx *c, int count, const uint8_t *const *values, const size_t *value_lens,
-                     uint8_t *shards_out, size_t shard_pitch, uint32_t *shard_lens_out, uint8_t *roots_out,
-                     uint8_t *branches_out, uint64_t *ticket) {
-    if (!c || count < 0 || (count > 0 && (!values || !value_lens || !shards_out || !roots_out)))
-        return RBC_ERR_INVALID_ARG;
-    if (count == 0) { if (ticket) *ticket = 0; return RBC_OK; }
-    size_t Smax = 0;
-    for (int i = 0; i < count; ++i) {
-        if (value_lens[i] == 0) return RBC_ERR_SHORT_DATA;  // Split: len(data) == 0
-        if (!values[i]) return RBC_ERR_INVALID_ARG;
-        Smax = std::max(Smax, (value_lens[i] + c->k - 1) / c->k);
-    }
-    if (shard_pitch < Smax) return RBC_ERR_INVALID_ARG;
-    // pinned output whose pitch the device rows can take: the device rows use
-    // it and the shards come back in ONE plain copy (pitch-to-pitch 2-D copies
-    // of many short rows ran at 0.1 GB/s at C4, and odd pitches off the copy
-    // engine's fast path); else whole HBM lines per row
-    const bool sh_direct = host_pinned(shards_out, ((size_t)count * c->n - 1) * shard_pitch + Smax);
-    const bool sh_flat = sh_direct && shard_pitch % kAlign == 0 && shard_pitch <= 0x7fffffffULL / c->n &&
-                         host_pinned(shards_out, (size_t)count * c->n * shard_pitch);  // the flat copy's extent
-    const size_t dpitch = sh_flat ? shard_pitch : round_up(Smax, 128);
-    const size_t vpitch = round_up((size_t)c->k * Smax + 32, kAlign);
-    if (vpitch > 0x7fffffffULL || (size_t)c->n * dpitch > 0x7fffffffULL) return RBC_ERR_INVALID_ARG;
-    const int d = c->depth, n = c->n;
-    const size_t sh_bytes = (size_t)count * n * dpitch, br_bytes = (size_t)count * n * std::max(d, 1) * 32;
-    std::lock_guard<std::mutex> lk(c->mu);
-    RBC_HIP(hipSetDevice(c->device));
-    Slot *sp = acquire_slot(c);
-    if (!sp) return RBC_ERR_DEVICE;
-    Slot &s = *sp;
+// lens: the host table [2*count] (value lengths, then shard lengths) in the
+// slot's pinned staging; d_vlens, d_slens: its two halves on the device
+struct ValueUpload {
+    const uint32_t *lens = nullptr, *d_vlens = nullptr, *d_slens = nullptr;
+};
+
+// The values and their length table onto the slot's device buffers (caller
+// holds c->mu): pinned values straight from where they are, pageable ones
+// through h_in [values, zero-filled to vpitch][lens] in one copy.  d_lens gets
+// `lens_tail` more bytes behind the table.
+int upload_values(const rbc_ctx *c, Slot &s, int count, const uint8_t *const *values, const size_t *value_lens,
+                  const ValueScan &v, size_t lens_tail, ValueUpload *u) {
+    const size_t vpitch = v.vpitch;
+    const int k = c->k;
     hipStream_t st = s.stream;
     RBC_HIP(s.d_values.ensure((size_t)count * vpitch));
-    RBC_HIP(s.d_shards.ensure(sh_bytes));
-    RBC_HIP(s.d_leaves.ensure((size_t)count * n * 32));
-    RBC_HIP(s.d_roots.ensure((size_t)count * 32));
-    RBC_HIP(s.d_branches.ensure(br_bytes));
-    RBC_HIP(s.d_lens.ensure((size_t)count * 8));
+    RBC_HIP(s.d_lens.ensure((size_t)count * 8 + lens_tail));
     // pinned staging only for what is not already pinned caller memory
     bool zc = false;
     const bool in_direct = values_pinned(values, value_lens, count, &zc);
     const size_t in_stage = in_direct ? 0 : (size_t)count * vpitch;
-    const bool rt_direct = host_pinned(roots_out, (size_t)count * 32);
-    const size_t br_out = (size_t)count * n * d * 32;
-    const bool br_direct = branches_out && d > 0 && host_pinned(branches_out, br_out);
     RBC_HIP(s.h_in.ensure(in_stage + (size_t)count * 8 + (in_direct ? (size_t)count * 8 : 0)));
-    RBC_HIP(s.h_out.ensure((sh_direct ? 0 : sh_bytes) + (size_t)count * 32 + br_bytes));
     uint8_t *stage = s.h_in.as<uint8_t>();
     uint32_t *lens = reinterpret_cast<uint32_t *>(stage + in_stage);
-    if (in_direct) {
-        // the encode kernel masks the Split pad (bytes past len are never used)
-        for (int i = 0; i < count; ++i) {
-            lens[i] = (uint32_t)value_lens[i];
-            lens[count + i] = (uint32_t)((value_lens[i] + c->k - 1) / c->k);
-        }
-        const int rc = upload_pinned_values(s, st, count, values, value_lens, vpitch, zc, lens,
-                                            reinterpret_cast<uint64_t *>(stage + in_stage + (size_t)count * 8));
-        if (rc) return rc;
-    } else {
-        parallel_for(count, vpitch, [&](int i) {
+    parallel_for(count, in_direct ? 0 : vpitch, [&](int i) {
+        if (!in_direct) {  // pinned values stay: the encode kernel masks the Split pad (bytes past len are never used)
             memcpy(stage + (size_t)i * vpitch, values[i], value_lens[i]);
             memset(stage + (size_t)i * vpitch + value_lens[i], 0, vpitch - value_lens[i]);
-            lens[i] = (uint32_t)value_lens[i];
-            lens[count + i] = (uint32_t)((value_lens[i] + c->k - 1) / c->k);
-        });
+        }
+        lens[i] = (uint32_t)value_lens[i];
+        lens[count + i] = (uint32_t)((value_lens[i] + k - 1) / k);
+    });
+    if (in_direct) {
+        const int rc = upload_pinned_values(s, st, count, values, value_lens, vpitch, zc, lens,
+                                            reinterpret_cast<uint64_t *>(lens + 2 * (size_t)count));
+        if (rc) return rc;
+    } else {
         RBC_HIP(hipMemcpyAsync(s.d_values.p, stage, (size_t)count * vpitch, hipMemcpyHostToDevice, st));
     }
     RBC_HIP(hipMemcpyAsync(s.d_lens.p, lens, (size_t)count * 8, hipMemcpyHostToDevice, st));
-    const uint32_t *d_vlens = s.d_lens.as<uint32_t>(), *d_slens = d_vlens + count;
-    int rc = stage_encode(c, st, count, s.d_values.as<uint8_t>(), vpitch, d_vlens, 0, s.d_shards.as<uint8_t>(),
-                          (uint32_t)dpitch);
-    if (!rc) rc = stage_leaves(c, st, count, s.d_shards.as<uint8_t>(), (uint32_t)dpitch, d_slens, 0,
-                               s.d_leaves.as<uint8_t>());
-    if (!rc) rc = stage_merkle_build(c, st, count, s.d_leaves.as<uint8_t>(), s.d_roots.as<uint8_t>(),
-                                     s.d_branches.as<uint8_t>());
-    if (rc) return rc;
-    uint8_t *o_sh = s.h_out.as<uint8_t>(), *o_rt = o_sh + (sh_direct ? 0 : sh_bytes),
-            *o_br = o_rt + (size_t)count * 32;
-    void *d_sh = s.d_shards.p, *d_rt = s.d_roots.p, *d_br = s.d_branches.p;
-    auto d2h = [=](hipStream_t cs) -> int {
-        if (sh_direct && dpitch == shard_pitch)  // every row whole: bytes [S_i, pitch) come back zero
-            RBC_HIP(hipMemcpyAsync(shards_out, d_sh, sh_bytes, hipMemcpyDeviceToHost, cs));
-        else if (sh_direct)  // Smax bytes per row: the device rows are zero past S_i
-            RBC_HIP(hipMemcpy2DAsync(shards_out, shard_pitch, d_sh, dpitch, Smax, (size_t)count * n,
-                                     hipMemcpyDeviceToHost, cs));
+    u->lens = lens;
+    u->d_vlens = s.d_lens.as<uint32_t>();
+    u->d_slens = u->d_vlens + count;
+    return RBC_OK;
+}
+
+// The rows a commit hands back: count * per rows of Smax bytes at the caller's
+// pitch, in one of three forms.  flat: pinned output whose pitch the device
+// rows can take -- the device rows use it and come back in ONE plain copy
+// (pitch-to-pitch 2-D copies of many short rows ran at 0.1 GB/s at C4, and odd
+// pitches off the copy engine's fast path).  direct only: pinned at another
+// pitch -- a 2-D copy of Smax bytes per row.  Neither: pageable -- one copy
+// into the h_out stage, a memcpy per row at completion.  The device rows are
+// zero past S_i, so every form returns bytes [S_i, Smax) (flat: [S_i, pitch))
+// zero.  The pointer queries are made here: construct it before taking c->mu.
+struct RowsOut {
+    uint8_t *out;
+    size_t pitch, Smax, rows;  // rows: count * per
+    bool direct, flat;
+    size_t dpitch, bytes;  // the device rows: their pitch, all of them
+    RowsOut(const rbc_ctx *c, int count, int per, uint8_t *out_, size_t pitch_, size_t Smax_)
+        : out(out_), pitch(pitch_), Smax(Smax_), rows((size_t)count * per) {
+        direct = rows > 0 && host_pinned(out, (rows - 1) * pitch + Smax);
+        flat = direct && pitch % kAlign == 0 && pitch <= 0x7fffffffULL / c->n &&
+               host_pinned(out, rows * pitch);  // the flat copy's extent
+        dpitch = flat ? pitch : round_up(Smax, 128);
+        bytes = rows * dpitch;
+    }
+    size_t stage_bytes() const { return direct ? 0 : bytes; }
+    int enqueue(hipStream_t cs, const void *d_rows, uint8_t *stage) const {
+        if (rows == 0) return RBC_OK;
+        if (direct && dpitch == pitch)  // every row whole
+            RBC_HIP(hipMemcpyAsync(out, d_rows, bytes, hipMemcpyDeviceToHost, cs));
+        else if (direct)
+            RBC_HIP(hipMemcpy2DAsync(out, pitch, d_rows, dpitch, Smax, rows, hipMemcpyDeviceToHost, cs));
         else
-            RBC_HIP(hipMemcpyAsync(o_sh, d_sh, sh_bytes, hipMemcpyDeviceToHost, cs));
-        RBC_HIP(hipMemcpyAsync(rt_direct ? roots_out : o_rt, d_rt, (size_t)count * 32, hipMemcpyDeviceToHost, cs));
-        if (branches_out && d > 0)
-            RBC_HIP(hipMemcpyAsync(br_direct ? branches_out : o_br, d_br, br_bytes, hipMemcpyDeviceToHost, cs));
+            RBC_HIP(hipMemcpyAsync(stage, d_rows, bytes, hipMemcpyDeviceToHost, cs));
         return RBC_OK;
-    };
+    }
+    void unstage(size_t first, size_t n_rows, const uint8_t *stage) const {  // pageable form only
+        for (size_t r = first; r < first + n_rows; ++r) memcpy(out + r * pitch, stage + r * dpitch, Smax);
+    }
+};
+
+// Roots [count][32] and branches [count][n][d][32] back to the caller: each
+// straight into pinned memory, else through the h_out stage [roots][branches]
+// and a memcpy at completion.  The device branches are [..][max(d, 1)][32];
+// branches_out == NULL or d == 0: no branches copied.
+struct HashesOut {
+    uint8_t *roots_out, *branches_out;
+    size_t rt_bytes, br_bytes, br_out;  // br_bytes: on the device; br_out: the caller's
+    bool rt_direct, br_direct;
+    HashesOut(const rbc_ctx *c, int count, uint8_t *roots, uint8_t *branches)
+        : roots_out(roots), branches_out(c->depth > 0 ? branches : nullptr), rt_bytes((size_t)count * 32),
+          br_bytes((size_t)count * c->n * std::max(c->depth, 1) * 32), br_out((size_t)count * c->n * c->depth * 32) {
+        rt_direct = host_pinned(roots_out, rt_bytes);
+        br_direct = branches_out && host_pinned(branches_out, br_out);
+    }
+    size_t stage_bytes() const { return rt_bytes + br_bytes; }
+    int enqueue(hipStream_t cs, const void *d_roots, const void *d_branches, uint8_t *stage) const {
+        RBC_HIP(hipMemcpyAsync(rt_direct ? roots_out : stage, d_roots, rt_bytes, hipMemcpyDeviceToHost, cs));
+        if (branches_out)
+            RBC_HIP(hipMemcpyAsync(br_direct ? branches_out : stage + rt_bytes, d_branches, br_bytes,
+                                   hipMemcpyDeviceToHost, cs));
+        return RBC_OK;
+    }
+    void finish(const uint8_t *stage) const {
+        if (!rt_direct) memcpy(roots_out, stage, rt_bytes);
+        if (branches_out && !br_direct) memcpy(branches_out, stage + rt_bytes, br_out);
+    }
+};
+
+// rbc_shard_commit (all n rows of an instance, from d_shards) and
+// rbc_shard_commit_parity (the p parity rows, from the dense arena d_parity;
+// the k data rows are hashed in d_shards and never copied back).
+int host_commit(rbc_ctx *c, int count, const uint8_t *const *values, const size_t *value_lens, const ValueScan &v,
+                bool parity_only, uint8_t *rows_out, size_t pitch, uint32_t *shard_lens_out, uint8_t *roots_out,
+                uint8_t *branches_out, uint64_t *ticket) {
+    const int n = c->n, per = parity_only ? c->p : n;
+    if (per > 0 && pitch < v.Smax) return RBC_ERR_INVALID_ARG;
+    const RowsOut ro(c, count, per, rows_out, pitch, v.Smax);
+    std::unique_lock<std::mutex> lk;
+    Slot *sp = open_slot(c, lk);
+    if (!sp) return RBC_ERR_DEVICE;
+    Slot &s = *sp;
+    const HashesOut ho(c, count, roots_out, branches_out);
+    RBC_HIP(s.d_shards.ensure((size_t)count * (parity_only ? c->k : n) * ro.dpitch));
+    if (parity_only) RBC_HIP(s.d_parity.ensure(ro.bytes));
+    RBC_HIP(s.d_leaves.ensure((size_t)count * n * 32));
+    RBC_HIP(s.d_roots.ensure(ho.rt_bytes));
+    RBC_HIP(s.d_branches.ensure(ho.br_bytes));
+    RBC_HIP(s.h_out.ensure(ro.stage_bytes() + ho.stage_bytes()));
+    ValueUpload u;
+    int rc = upload_values(c, s, count, values, value_lens, v, 0, &u);
+    if (rc) return rc;
+    Rows rows{s.d_shards.as<uint8_t>(), (uint32_t)ro.dpitch};
+    if (parity_only) {
+        rows.split = true;
+        rows.parity = s.d_parity.as<uint8_t>();
+    }
+    rc = commit_stages(c, s.stream, count, s.d_values.as<uint8_t>(), v.vpitch, u.d_vlens, 0, rows, u.d_slens,
+                       s.d_leaves.as<uint8_t>(), s.d_roots.as<uint8_t>(), s.d_branches.as<uint8_t>());
+    if (rc) return rc;
+    uint8_t *o_rows = s.h_out.as<uint8_t>(), *o_hash = o_rows + ro.stage_bytes();
+    const void *d_rows = parity_only ? s.d_parity.p : s.d_shards.p, *d_rt = s.d_roots.p, *d_br = s.d_branches.p;
+    const uint32_t *slens = u.lens + count;
+    const size_t Smax = v.Smax;
     return submit(c, s, ticket, [=]() {
-        parallel_for(count, sh_direct ? 0 : (size_t)n * Smax, [&](int i) {
-            const size_t S = lens[count + i];
-            if (!sh_direct)
-                for (int j = 0; j < n; ++j)
-                    memcpy(shards_out + ((size_t)i * n + j) * shard_pitch, o_sh + ((size_t)i * n + j) * dpitch, Smax);
-            if (shard_lens_out) shard_lens_out[i] = (uint32_t)S;
+        parallel_for(count, ro.direct ? 0 : (size_t)per * Smax, [&](int i) {
+            if (!ro.direct) ro.unstage((size_t)i * per, per, o_rows);
+            if (shard_lens_out) shard_lens_out[i] = slens[i];
         });
-        if (!rt_direct) memcpy(roots_out, o_rt, (size_t)count * 32);
-        if (branches_out && d > 0 && !br_direct) memcpy(branches_out, o_br, br_out);
+        ho.finish(o_hash);
         return RBC_OK;
-    }, d2h);
+    }, [=](hipStream_t cs) -> int {
+        const int rc = ro.enqueue(cs, d_rows, o_rows);
+        return rc ? rc : ho.enqueue(cs, d_rt, d_br, o_hash);
+    });
+}
+
+}  // namespace
+}  // extern "C++"
+
+int rbc_shard_commit(rbc_ctx *c, int count, const uint8_t *const *values, const size_t *value_lens,
+                     uint8_t *shards_out, size_t shard_pitch, uint32_t *shard_lens_out, uint8_t *roots_out,
+                     uint8_t *branches_out, uint64_t *ticket) {
+    ValueScan v;
+    const int rc = scan_values(c, count, values, value_lens, shards_out && roots_out, ticket, &v);
+    if (rc || count == 0) return rc;
+    return host_commit(c, count, values, value_lens, v, false, shards_out, shard_pitch, shard_lens_out, roots_out,
+                       branches_out, ticket);
 }
 
 // rbc_shard_commit for a caller that keeps Split's data rows as slices of its
 // own value (klauspost Split / Encode, rbc/rbc.go:97-100): only the p parity
-// rows of each instance cross PCIe, from the dense arena the encoder wrote
-// them to ([count][p][dpitch], stage_encode_parity) in one linear copy.
+// rows of each instance cross PCIe.
 int rbc_shard_commit_parity(rbc_ctx *c, int count, const uint8_t *const *values, const size_t *value_lens,
                             uint8_t *parity_out, size_t parity_pitch, uint32_t *shard_lens_out, uint8_t *roots_out,
                             uint8_t *branches_out, uint64_t *ticket) {
-    if (!c || count < 0 || (count > 0 && (!values || !value_lens || !roots_out || (c->p > 0 && !parity_out))))
-        return RBC_ERR_INVALID_ARG;
-    if (count == 0) { if (ticket) *ticket = 0; return RBC_OK; }
-    size_t Smax = 0;
-    for (int i = 0; i < count; ++i) {
-        if (value_lens[i] == 0) return RBC_ERR_SHORT_DATA;  // Split: len(data) == 0
-        if (!values[i]) return RBC_ERR_INVALID_ARG;
-        Smax = std::max(Smax, (value_lens[i] + c->k - 1) / c->k);
-    }
-    const int d = c->depth, n = c->n, k = c->k, p = c->p;
-    if (p > 0 && parity_pitch < Smax) return RBC_ERR_INVALID_ARG;
-    const size_t vpitch = round_up((size_t)k * Smax + 32, kAlign);
-    if (vpitch > 0x7fffffffULL || (size_t)n * round_up(Smax, 128) > 0x7fffffffULL) return RBC_ERR_INVALID_ARG;
-    // the three output forms of rbc_shard_commit, over p rows per instance
-    const bool par_direct = p > 0 && host_pinned(parity_out, ((size_t)count * p - 1) * parity_pitch + Smax);
-    const bool par_flat = par_direct && parity_pitch % kAlign == 0 && parity_pitch <= 0x7fffffffULL / n &&
-                          host_pinned(parity_out, (size_t)count * p * parity_pitch);  // the flat copy's extent
-    const size_t dpitch = par_flat ? parity_pitch : round_up(Smax, 128);
-    const size_t par_bytes = (size_t)count * p * dpitch, br_bytes = (size_t)count * n * std::max(d, 1) * 32;
-    std::lock_guard<std::mutex> lk(c->mu);
-    RBC_HIP(hipSetDevice(c->device));
-    Slot *sp = acquire_slot(c);
-    if (!sp) return RBC_ERR_DEVICE;
-    Slot &s = *sp;
-    hipStream_t st = s.stream;
-    RBC_HIP(s.d_values.ensure((size_t)count * vpitch));
-    RBC_HIP(s.d_shards.ensure((size_t)count * k * dpitch));  // the data rows: hashed, never copied back
-    RBC_HIP(s.d_parity.ensure(par_bytes));
-    RBC_HIP(s.d_leaves.ensure((size_t)count * n * 32));
-    RBC_HIP(s.d_roots.ensure((size_t)count * 32));
-    RBC_HIP(s.d_branches.ensure(br_bytes));
-    RBC_HIP(s.d_lens.ensure((size_t)count * 8));
-    bool zc = false;
-    const bool in_direct = values_pinned(values, value_lens, count, &zc);
-    const size_t in_stage = in_direct ? 0 : (size_t)count * vpitch;
-    const bool rt_direct = host_pinned(roots_out, (size_t)count * 32);
-    const size_t br_out = (size_t)count * n * d * 32;
-    const bool br_direct = branches_out && d > 0 && host_pinned(branches_out, br_out);
-    RBC_HIP(s.h_in.ensure(in_stage + (size_t)count * 8 + (in_direct ? (size_t)count * 8 : 0)));
-    RBC_HIP(s.h_out.ensure((par_direct ? 0 : par_bytes) + (size_t)count * 32 + br_bytes));
-    uint8_t *stage = s.h_in.as<uint8_t>();
-    uint32_t *lens = reinterpret_cast<uint32_t *>(stage + in_stage);
-    if (in_direct) {
-        for (int i = 0; i < count; ++i) {
-            lens[i] = (uint32_t)value_lens[i];
-            lens[count + i] = (uint32_t)((value_lens[i] + k - 1) / k);
-        }
-        const int rc = upload_pinned_values(s, st, count, values, value_lens, vpitch, zc, lens,
-                                            reinterpret_cast<uint64_t *>(stage + in_stage + (size_t)count * 8));
-        if (rc) return rc;
-    } else {
-        parallel_for(count, vpitch, [&](int i) {
-            memcpy(stage + (size_t)i * vpitch, values[i], value_lens[i]);
-            memset(stage + (size_t)i * vpitch + value_lens[i], 0, vpitch - value_lens[i]);
-            lens[i] = (uint32_t)value_lens[i];
-            lens[count + i] = (uint32_t)((value_lens[i] + k - 1) / k);
-        });
-        RBC_HIP(hipMemcpyAsync(s.d_values.p, stage, (size_t)count * vpitch, hipMemcpyHostToDevice, st));
-    }
-    RBC_HIP(hipMemcpyAsync(s.d_lens.p, lens, (size_t)count * 8, hipMemcpyHostToDevice, st));
-    const uint32_t *d_vlens = s.d_lens.as<uint32_t>(), *d_slens = d_vlens + count;
-    int rc = stage_encode_parity(c, st, count, s.d_values.as<uint8_t>(), vpitch, d_vlens, 0, s.d_shards.as<uint8_t>(),
-                                 s.d_parity.as<uint8_t>(), (uint32_t)dpitch);
-    if (!rc) rc = stage_leaves_parity(c, st, count, s.d_shards.as<uint8_t>(), s.d_parity.as<uint8_t>(),
-                                      (uint32_t)dpitch, d_slens, 0, s.d_leaves.as<uint8_t>());
-    if (!rc) rc = stage_merkle_build(c, st, count, s.d_leaves.as<uint8_t>(), s.d_roots.as<uint8_t>(),
-                                     s.d_branches.as<uint8_t>());
-    if (rc) return rc;
-    uint8_t *o_par = s.h_out.as<uint8_t>(), *o_rt = o_par + (par_direct ? 0 : par_bytes),
-            *o_br = o_rt + (size_t)count * 32;
-    void *d_par = s.d_parity.p, *d_rt = s.d_roots.p, *d_br = s.d_branches.p;
-    auto d2h = [=](hipStream_t cs) -> int {
-        if (p > 0) {
-            if (par_direct && dpitch == parity_pitch)  // ONE linear copy: bytes [S_i, pitch) come back zero
-                RBC_HIP(hipMemcpyAsync(parity_out, d_par, par_bytes, hipMemcpyDeviceToHost, cs));
-            else if (par_direct)  // Smax bytes per row: the arena rows are zero past S_i
-                RBC_HIP(hipMemcpy2DAsync(parity_out, parity_pitch, d_par, dpitch, Smax, (size_t)count * p,
-                                         hipMemcpyDeviceToHost, cs));
-            else
-                RBC_HIP(hipMemcpyAsync(o_par, d_par, par_bytes, hipMemcpyDeviceToHost, cs));
-        }
-        RBC_HIP(hipMemcpyAsync(rt_direct ? roots_out : o_rt, d_rt, (size_t)count * 32, hipMemcpyDeviceToHost, cs));
-        if (branches_out && d > 0)
-            RBC_HIP(hipMemcpyAsync(br_direct ? branches_out : o_br, d_br, br_bytes, hipMemcpyDeviceToHost, cs));
-        return RBC_OK;
-    };
-    return submit(c, s, ticket, [=]() {
-        parallel_for(count, par_direct ? 0 : (size_t)p * Smax, [&](int i) {
-            if (!par_direct)
-                for (int j = 0; j < p; ++j)
-                    memcpy(parity_out + ((size_t)i * p + j) * parity_pitch, o_par + ((size_t)i * p + j) * dpitch, Smax);
-            if (shard_lens_out) shard_lens_out[i] = lens[count + i];
-        });
-        if (!rt_direct) memcpy(roots_out, o_rt, (size_t)count * 32);
-        if (branches_out && d > 0 && !br_direct) memcpy(branches_out, o_br, br_out);
-        return RBC_OK;
-    }, d2h);
+    ValueScan v;
+    const int rc = scan_values(c, count, values, value_lens, roots_out && (parity_out || (c && c->p == 0)), ticket, &v);
+    if (rc || count == 0) return rc;
+    return host_commit(c, count, values, value_lens, v, true, parity_out, parity_pitch, shard_lens_out, roots_out,
+                       branches_out, ticket);
 }
 
 // VAL hand-off: shard + commit on the device, marshal the
@@ -1932,68 +1835,35 @@ int rbc_shard_commit_parity(rbc_ctx *c, int count, const uint8_t *const *values,
 int rbc_shard_commit_val(rbc_ctx *c, int count, const uint8_t *const *values, const size_t *value_lens,
                          uint8_t *msgs, size_t msg_pitch, uint32_t *msg_lens, uint8_t *roots_out,
                          uint64_t *ticket) {
-    if (!c || count < 0 || (count > 0 && (!values || !value_lens || !msgs || !msg_lens))) return RBC_ERR_INVALID_ARG;
-    if (count == 0) { if (ticket) *ticket = 0; return RBC_OK; }
-    size_t Smax = 0;
-    for (int i = 0; i < count; ++i) {
-        if (value_lens[i] == 0) return RBC_ERR_SHORT_DATA;  // Split: len(data) == 0
-        if (!values[i]) return RBC_ERR_INVALID_ARG;
-        Smax = std::max(Smax, (value_lens[i] + c->k - 1) / c->k);
-    }
+    ValueScan v;
+    int rc = scan_values(c, count, values, value_lens, msgs && msg_lens, ticket, &v);
+    if (rc || count == 0) return rc;
     const int d = c->depth, n = c->n;
     const int codec = c->wire_codec;
-    const size_t need = round_up(std::max(rbc_val_message_bytes_codec(codec, n, d, (uint32_t)Smax, 0, RBC_MSG_VAL),
-                                          rbc_val_message_bytes_codec(codec, n, d, (uint32_t)Smax, (uint32_t)(n - 1),
+    const uint32_t Smax = (uint32_t)v.Smax;
+    const size_t need = round_up(std::max(rbc_val_message_bytes_codec(codec, n, d, Smax, 0, RBC_MSG_VAL),
+                                          rbc_val_message_bytes_codec(codec, n, d, Smax, (uint32_t)(n - 1),
                                                                       RBC_MSG_VAL)),
                                  16);
     if (msg_pitch < need || msg_pitch % 16) return RBC_ERR_INVALID_ARG;
-    const size_t dpitch = round_up(Smax, 128);
-    const size_t vpitch = round_up((size_t)c->k * Smax + 32, kAlign);
-    if (vpitch > 0x7fffffffULL || (size_t)n * dpitch > 0x7fffffffULL) return RBC_ERR_INVALID_ARG;
-    const size_t sh_bytes = (size_t)count * n * dpitch, br_bytes = (size_t)count * n * std::max(d, 1) * 32;
-    const size_t msg_bytes = (size_t)count * n * msg_pitch;
-    std::lock_guard<std::mutex> lk(c->mu);
-    RBC_HIP(hipSetDevice(c->device));
-    Slot *sp = acquire_slot(c);
+    const size_t dpitch = round_up(v.Smax, 128);
+    const size_t sh_bytes = (size_t)count * n * dpitch, msg_bytes = (size_t)count * n * msg_pitch;
+    std::unique_lock<std::mutex> lk;
+    Slot *sp = open_slot(c, lk);
     if (!sp) return RBC_ERR_DEVICE;
     Slot &s = *sp;
     hipStream_t st = s.stream;
-    RBC_HIP(s.d_values.ensure((size_t)count * vpitch));
     RBC_HIP(s.d_shards.ensure(sh_bytes + msg_bytes));  // shards, then the messages
     RBC_HIP(s.d_leaves.ensure((size_t)count * n * 32));
     RBC_HIP(s.d_roots.ensure((size_t)count * 32));
-    RBC_HIP(s.d_branches.ensure(br_bytes));
-    RBC_HIP(s.d_lens.ensure((size_t)count * 8 + (size_t)count * n * 4));
-    RBC_HIP(s.h_in.ensure((size_t)count * vpitch + (size_t)count * 16));
-    uint8_t *stage = s.h_in.as<uint8_t>();
-    uint32_t *lens = reinterpret_cast<uint32_t *>(stage + (size_t)count * vpitch);
-    bool zc = false;
-    const bool in_direct = values_pinned(values, value_lens, count, &zc);
-    if (in_direct) {  // pinned values: one DMA each (or one gather), the encode kernel masks the Split pad
-        for (int i = 0; i < count; ++i) {
-            lens[i] = (uint32_t)value_lens[i];
-            lens[count + i] = (uint32_t)((value_lens[i] + c->k - 1) / c->k);
-        }
-        const int rc = upload_pinned_values(s, st, count, values, value_lens, vpitch, zc, lens,
-                                            reinterpret_cast<uint64_t *>(lens + 2 * (size_t)count));
-        if (rc) return rc;
-    } else {
-        parallel_for(count, vpitch, [&](int i) {
-            memcpy(stage + (size_t)i * vpitch, values[i], value_lens[i]);
-            memset(stage + (size_t)i * vpitch + value_lens[i], 0, vpitch - value_lens[i]);
-            lens[i] = (uint32_t)value_lens[i];
-            lens[count + i] = (uint32_t)((value_lens[i] + c->k - 1) / c->k);
-        });
-        RBC_HIP(hipMemcpyAsync(s.d_values.p, stage, (size_t)count * vpitch, hipMemcpyHostToDevice, st));
-    }
-    RBC_HIP(hipMemcpyAsync(s.d_lens.p, lens, (size_t)count * 8, hipMemcpyHostToDevice, st));
-    const uint32_t *d_vlens = s.d_lens.as<uint32_t>(), *d_slens = d_vlens + count;
+    RBC_HIP(s.d_branches.ensure((size_t)count * n * std::max(d, 1) * 32));
+    ValueUpload u;
+    rc = upload_values(c, s, count, values, value_lens, v, (size_t)count * n * 4, &u);  // + the message lengths
+    if (rc) return rc;
     uint32_t *d_mlens = s.d_lens.as<uint32_t>() + 2 * (size_t)count;
     uint8_t *d_sh = s.d_shards.as<uint8_t>(), *d_msgs = d_sh + sh_bytes;
-    int rc = stage_encode(c, st, count, s.d_values.as<uint8_t>(), vpitch, d_vlens, 0, d_sh, (uint32_t)dpitch);
-    if (!rc) rc = stage_leaves(c, st, count, d_sh, (uint32_t)dpitch, d_slens, 0, s.d_leaves.as<uint8_t>());
-    if (!rc) rc = stage_merkle_build(c, st, count, s.d_leaves.as<uint8_t>(), s.d_roots.as<uint8_t>(),
-                                     s.d_branches.as<uint8_t>());
+    rc = commit_stages(c, st, count, s.d_values.as<uint8_t>(), v.vpitch, u.d_vlens, 0, {d_sh, (uint32_t)dpitch},
+                       u.d_slens, s.d_leaves.as<uint8_t>(), s.d_roots.as<uint8_t>(), s.d_branches.as<uint8_t>());
     if (rc) return rc;
     WireArgs a{};
     a.count = count;
@@ -2003,7 +1873,7 @@ int rbc_shard_commit_val(rbc_ctx *c, int count, const uint8_t *const *values, co
     a.shards = d_sh;
     a.inst_pitch = (uint64_t)n * dpitch;
     a.row_pitch = (uint32_t)dpitch;
-    a.lens = d_slens;
+    a.lens = u.d_slens;
     a.branches = s.d_branches.as<uint8_t>();
     a.roots = s.d_roots.as<uint8_t>();
     a.out = d_msgs;
@@ -2036,9 +1906,8 @@ int rbc_validate_batch(rbc_ctx *c, int count, const uint8_t *const *shards, cons
     const size_t pitch = round_up(Smax, kAlign);
     const size_t bslot = (size_t)std::max(d, 1) * 32;
     if ((size_t)count * pitch > 0x7fffffffULL) return RBC_ERR_INVALID_ARG;
-    std::lock_guard<std::mutex> lk(c->mu);
-    RBC_HIP(hipSetDevice(c->device));
-    Slot *sp = acquire_slot(c);
+    std::unique_lock<std::mutex> lk;
+    Slot *sp = open_slot(c, lk);
     if (!sp) return RBC_ERR_DEVICE;
     Slot &s = *sp;
     hipStream_t st = s.stream;
@@ -2181,9 +2050,8 @@ static int validate_packed(rbc_ctx *c, int count, const uint8_t *arena, size_t a
     // buffer naming only the received rows): gather the named bytes over PCIe
     // instead of moving the whole arena
     const uint8_t *zc = named < arena_bytes / 4 * 3 ? host_zero_copy(arena, arena_bytes) : nullptr;
-    std::lock_guard<std::mutex> lk(c->mu);
-    RBC_HIP(hipSetDevice(c->device));
-    Slot *sp = acquire_slot(c);
+    std::unique_lock<std::mutex> lk;
+    Slot *sp = open_slot(c, lk);
     if (!sp) return RBC_ERR_DEVICE;
     Slot &s = *sp;
     hipStream_t st = s.stream;
@@ -2314,22 +2182,21 @@ static int host_receive(rbc_ctx *c, int count, const uint8_t *shards, size_t sha
     // what is not already pinned caller memory
     bool uniform = true;
     for (int i = 0; i < count && uniform; ++i) uniform = shard_lens[i] == Smax;
-    const bool in_direct = !dev_rows && uniform && host_pinned(shards, ((size_t)count * n_of(c) - 1) * shard_pitch + Smax);
-    const uint8_t *zc = in_direct ? host_zero_copy(shards, ((size_t)count * n_of(c) - 1) * shard_pitch + Smax)
+    const bool in_direct = !dev_rows && uniform && host_pinned(shards, ((size_t)count * c->n - 1) * shard_pitch + Smax);
+    const uint8_t *zc = in_direct ? host_zero_copy(shards, ((size_t)count * c->n - 1) * shard_pitch + Smax)
                                   : nullptr;
     // a pinned batch whose pitch the device rows can take moves in ONE plain
     // copy (a pitched 2-D copy runs as a blit kernel)
     const bool flat = in_direct && !zc && shard_pitch % kAlign == 0 &&
-                      host_pinned(shards, (size_t)count * n_of(c) * shard_pitch);  // the flat copy's extent
+                      host_pinned(shards, (size_t)count * c->n * shard_pitch);  // the flat copy's extent
     const size_t dpitch = flat ? shard_pitch : round_up(Smax, 128);
     const size_t vpitch = round_up((size_t)c->k * Smax, 16);
     if ((size_t)c->n * dpitch > 0x7fffffffULL || vpitch > 0x7fffffffULL) return RBC_ERR_INVALID_ARG;
     const int n = c->n, k = c->k, d = c->depth;
     const size_t sh_bytes = (size_t)count * n * dpitch;
     const size_t br_bytes = (size_t)count * n * std::max(d, 1) * 32;
-    std::lock_guard<std::mutex> lk(c->mu);
-    RBC_HIP(hipSetDevice(c->device));
-    Slot *sp = acquire_slot(c);
+    std::unique_lock<std::mutex> lk;
+    Slot *sp = open_slot(c, lk);
     if (!sp) return RBC_ERR_DEVICE;
     Slot &s = *sp;
     hipStream_t st = s.stream;
@@ -2599,9 +2466,8 @@ int rbc_interpolate(rbc_ctx *c, const uint8_t *root, const uint8_t *const *shard
     const int n = c->n, k = c->k;
     const size_t dpitch = round_up(S, 128), vpitch = round_up((size_t)k * S, 16);
     if ((size_t)n * dpitch > 0x7fffffffULL || vpitch > 0x7fffffffULL) return RBC_ERR_INVALID_ARG;
-    std::lock_guard<std::mutex> lk(c->mu);
-    RBC_HIP(hipSetDevice(c->device));
-    Slot *sp = acquire_slot(c);
+    std::unique_lock<std::mutex> lk;
+    Slot *sp = open_slot(c, lk);
     if (!sp) return RBC_ERR_DEVICE;
     Slot &s = *sp;
     hipStream_t st = s.stream;
@@ -2690,7 +2556,7 @@ static int rs_parity(rbc_ctx *c, const uint8_t *const *shards, size_t S, std::ve
     for (int j = 0; j < c->k; ++j) memcpy(stage + (size_t)j * S, shards[j], S);
     RBC_HIP(hipMemcpyAsync(c->d_values.p, stage, vpitch, hipMemcpyHostToDevice, st));
     int rc = stage_encode(c, st, 1, c->d_values.as<uint8_t>(), vpitch, nullptr, (uint32_t)((size_t)c->k * S),
-                          c->d_shards.as<uint8_t>(), (uint32_t)dpitch);
+                          {c->d_shards.as<uint8_t>(), (uint32_t)dpitch});
     if (rc) return rc;
     parity.assign((size_t)c->p * S, 0);
     if (c->p > 0)

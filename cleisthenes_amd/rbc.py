@@ -376,6 +376,28 @@ class Context:
         return {"value": bytes(value[: vlen.value]), "digest": bytes(dig)}
 
     # ---- host batch API ---------------------------------------------------
+    def _commit_values(self, values: Sequence[bytes]):
+        """(arrs, Smax, vlens, vptrs) of a shard-commit submission's values."""
+        arrs = [v if isinstance(v, np.ndarray) and v.dtype == np.uint8 and v.flags.c_contiguous
+                else _bytes_array(v) for v in values]
+        Smax = max((len(a) + self.k - 1) // self.k for a in arrs)
+        vlens = (c_size_t * len(arrs))(*[len(a) for a in arrs])
+        vptrs = (c_void_p * len(arrs))(*[a.ctypes.data if len(a) else None for a in arrs])
+        return arrs, Smax, vlens, vptrs
+
+    def _commit_outputs(self, out: Optional[dict], key: str, count: int, rows: int, Smax: int):
+        """(rows, roots, branches) of a shard commit with `rows` rows per
+        instance: out[key] [count][rows][pitch >= Smax], out["roots"] and
+        out["branches"] checked, or fresh arrays at pitch Smax."""
+        bshape = (count, self.n, max(self.depth, 1), 32)
+        if out is None:
+            return (np.zeros((count, rows, Smax), dtype=np.uint8), np.zeros((count, 32), dtype=np.uint8),
+                    np.zeros(bshape, dtype=np.uint8))
+        arr, roots, br = out[key], out["roots"], out["branches"]
+        assert arr.shape[:2] == (count, rows) and arr.shape[2] >= Smax and arr.flags.c_contiguous
+        assert roots.shape == (count, 32) and br.shape == bshape
+        return arr, roots, br
+
     def shard_commit_batch(self, values: Sequence[bytes]) -> dict:
         return self.shard_commit_submit(values).wait()
 
@@ -385,23 +407,11 @@ class Context:
         `out` may hold preallocated (e.g. pinned_empty) "shards" [count][N][Smax],
         "roots" [count][32] and "branches" [count][N][max(d,1)][32] arrays."""
         count = len(values)
-        arrs = [v if isinstance(v, np.ndarray) and v.dtype == np.uint8 and v.flags.c_contiguous
-                else _bytes_array(v) for v in values]
-        Smax = max((len(a) + self.k - 1) // self.k for a in arrs)
-        pitch = Smax
-        bshape = (count, self.n, max(self.depth, 1), 32)
-        if out is not None:  # out["shards"] may be [count][N][pitch >= Smax] (a 64-B pitch: one D2H copy)
-            shards, roots, br = out["shards"], out["roots"], out["branches"]
-            pitch = shards.shape[2]
-            assert shards.shape[:2] == (count, self.n) and pitch >= Smax and shards.flags.c_contiguous
-            assert roots.shape == (count, 32) and br.shape == bshape
-        else:
-            shards = np.zeros((count, self.n, pitch), dtype=np.uint8)
-            roots = np.zeros((count, 32), dtype=np.uint8)
-            br = np.zeros(bshape, dtype=np.uint8)
+        arrs, Smax, vlens, vptrs = self._commit_values(values)
+        # out["shards"] may be [count][N][pitch >= Smax] (a 64-B pitch: one D2H copy)
+        shards, roots, br = self._commit_outputs(out, "shards", count, self.n, Smax)
+        pitch = shards.shape[2]
         slens = np.zeros(count, dtype=np.uint32)
-        vlens = (c_size_t * count)(*[len(a) for a in arrs])
-        vptrs = (c_void_p * count)(*[a.ctypes.data if len(a) else None for a in arrs])
         t = c_uint64(0)
         check(lib.rbc_shard_commit(self._p, count, vptrs, vlens, _ptr(shards), pitch,
                                    slens.ctypes.data_as(_lib.u32p), _ptr(roots), _ptr(br), byref(t)),
@@ -447,23 +457,10 @@ class Context:
         linear D2H copy), "roots" [count][32] and "branches"
         [count][N][max(d,1)][32] arrays."""
         count = len(values)
-        arrs = [v if isinstance(v, np.ndarray) and v.dtype == np.uint8 and v.flags.c_contiguous
-                else _bytes_array(v) for v in values]
-        Smax = max((len(a) + self.k - 1) // self.k for a in arrs)
-        pitch = Smax
-        bshape = (count, self.n, max(self.depth, 1), 32)
-        if out is not None:
-            parity, roots, br = out["parity"], out["roots"], out["branches"]
-            pitch = parity.shape[2]
-            assert parity.shape[:2] == (count, self.p) and pitch >= Smax and parity.flags.c_contiguous
-            assert roots.shape == (count, 32) and br.shape == bshape
-        else:
-            parity = np.zeros((count, self.p, pitch), dtype=np.uint8)
-            roots = np.zeros((count, 32), dtype=np.uint8)
-            br = np.zeros(bshape, dtype=np.uint8)
+        arrs, Smax, vlens, vptrs = self._commit_values(values)
+        parity, roots, br = self._commit_outputs(out, "parity", count, self.p, Smax)
+        pitch = parity.shape[2]
         slens = np.zeros(count, dtype=np.uint32)
-        vlens = (c_size_t * count)(*[len(a) for a in arrs])
-        vptrs = (c_void_p * count)(*[a.ctypes.data if len(a) else None for a in arrs])
         t = c_uint64(0)
         check(lib.rbc_shard_commit_parity(self._p, count, vptrs, vlens, _ptr(parity) if self.p else None, pitch,
                                           slens.ctypes.data_as(_lib.u32p), _ptr(roots), _ptr(br), byref(t)),
@@ -481,9 +478,7 @@ class Context:
     def shard_commit_val_submit(self, values: Sequence[bytes], ring: Optional[np.ndarray] = None) -> "HostTicket":
         """Asynchronous rbc_shard_commit_val (see shard_commit_submit)."""
         count = len(values)
-        arrs = [v if isinstance(v, np.ndarray) and v.dtype == np.uint8 and v.flags.c_contiguous
-                else _bytes_array(v) for v in values]
-        Smax = max((len(a) + self.k - 1) // self.k for a in arrs)
+        arrs, Smax, vlens, vptrs = self._commit_values(values)
         need = max(self.val_message_size(Smax, 0, 0), self.val_message_size(Smax, self.n - 1, 0))
         pitch = (need + 15) // 16 * 16
         if ring is None:
@@ -491,8 +486,6 @@ class Context:
         assert ring.shape[:2] == (count, self.n) and ring.shape[2] % 16 == 0 and ring.shape[2] >= pitch
         lens = np.zeros((count, self.n), dtype=np.uint32)
         roots = np.zeros((count, 32), dtype=np.uint8)
-        vlens = (c_size_t * count)(*[len(a) for a in arrs])
-        vptrs = (c_void_p * count)(*[a.ctypes.data if len(a) else None for a in arrs])
         t = c_uint64(0)
         check(lib.rbc_shard_commit_val(self._p, count, vptrs, vlens, _ptr(ring), ring.shape[2],
                                        lens.ctypes.data_as(_lib.u32p), _ptr(roots), byref(t)), "rbc_shard_commit_val")

@@ -13,10 +13,12 @@
 #include <stdlib.h>
 #include <string.h>
 
+#include <memory>
 #include <random>
 #include <vector>
 
 #include "../../include/rbc_gpu.h"
+#include "../../include/rbc_protocol.h"
 
 static std::mt19937_64 rng;
 static int fails = 0;
@@ -84,30 +86,94 @@ static void fuzz_validate_batch(Geo &g) {
         if (!sp[i] || !rp[i] || idx[i] >= (uint32_t)g.n || sl[i] == 0) EXPECT(ok[i] == 0);
 }
 
+// A caller buffer of exactly `bytes` bytes, pinned (rbc_host_alloc) or on the heap
+struct Buf {
+    uint8_t *p = nullptr;
+    bool pinned;
+    Buf(size_t bytes, bool pin) : pinned(pin) {
+        if (pinned) {
+            void *q = nullptr;
+            EXPECT(rbc_host_alloc(bytes ? bytes : 1, &q) == RBC_OK);
+            p = (uint8_t *)q;
+        } else {
+            p = (uint8_t *)malloc(bytes ? bytes : 1);
+        }
+    }
+    Buf(const Buf &) = delete;
+    ~Buf() {
+        if (pinned) rbc_host_free(p);
+        else free(p);
+    }
+};
+
+// The three commit entry points over their shared host path: values and every
+// output drawn independently from pinned memory or the heap, the row pitch from
+// the three output forms (and sometimes too small), now and then 64 or more
+// short pinned values (the gather upload).
 static void fuzz_shard_commit(Geo &g) {
-    const int count = (int)rnd(6);
-    std::vector<std::vector<uint8_t>> val(count);
+    const int entry = (int)rnd(3);  // rbc_shard_commit, _parity, _val
+    const bool many = coin(6);
+    const int count = many ? 64 + (int)rnd(8) : (int)rnd(6);
+    const bool vpin = many ? coin(85) : coin(50);
+    // a context of its own now and then: its slots' buffers have not grown in earlier calls
+    rbc_ctx *ctx = g.ctx;
+    const bool fresh = many || coin(10);
+    if (fresh) EXPECT(rbc_ctx_create(g.n, g.f, 0, &ctx) == RBC_OK);
+    std::vector<std::unique_ptr<Buf>> val(count);
     std::vector<const uint8_t *> vp(count);
     std::vector<size_t> vl(count);
     size_t Smax = 0;
     bool empty = false;
     for (int i = 0; i < count; ++i) {
-        vl[i] = rlen(4000);
+        vl[i] = many ? (coin(97) ? 1 + rnd(200) : 0) : rlen(4000);
         empty |= vl[i] == 0;
-        val[i] = bytes(vl[i]);
-        vp[i] = vl[i] ? val[i].data() : (coin(50) ? nullptr : val[i].data());
+        val[i] = std::make_unique<Buf>(vl[i], vpin && !coin(3));
+        for (size_t b = 0; b < vl[i]; ++b) val[i]->p[b] = (uint8_t)rng();
+        vp[i] = vl[i] ? val[i]->p : (coin(50) ? nullptr : val[i]->p);
         Smax = std::max(Smax, (vl[i] + g.k - 1) / g.k);
     }
-    const size_t pitch = coin(80) ? Smax + rnd(70) : rnd(Smax + 1);
-    std::vector<uint8_t> shards((size_t)count * g.n * pitch + 1), roots((size_t)count * 32 + 1);
-    std::vector<uint8_t> br((size_t)count * g.n * std::max(g.d, 1) * 32 + 1);
-    std::vector<uint32_t> slens(count + 1);
+    const int p = g.n - g.k, rows = entry == 1 ? p : g.n;
+    const int d1 = std::max(g.d, 1);
+    Buf roots((size_t)count * 32, coin(50)), br((size_t)count * g.n * d1 * 32, coin(50));
     uint64_t t = 0;
     const bool async = coin(50);
-    const int rc = rbc_shard_commit(g.ctx, count, vp.data(), vl.data(), shards.data(), pitch, slens.data(),
-                                    roots.data(), coin(30) ? nullptr : br.data(), async ? &t : nullptr);
+    int rc;
+    bool bad_pitch;
+    std::vector<uint32_t> slens(count + 1, 0xffffffffu);
+    if (entry < 2) {
+        size_t pitch;
+        switch (rnd(5)) {
+            case 0: pitch = Smax; break;
+            case 1: pitch = Smax + 3; break;
+            case 2: pitch = (Smax + 63) / 64 * 64; break;
+            case 3: pitch = Smax + rnd(70); break;
+            default: pitch = rnd(Smax + 1); break;
+        }
+        bad_pitch = pitch < Smax;
+        Buf out((size_t)count * rows * pitch, coin(50));
+        uint8_t *bp = coin(30) ? nullptr : br.p;
+        rc = entry == 0 ? rbc_shard_commit(ctx, count, vp.data(), vl.data(), out.p, pitch, slens.data(), roots.p, bp,
+                                           async ? &t : nullptr)
+                        : rbc_shard_commit_parity(ctx, count, vp.data(), vl.data(), out.p, pitch, slens.data(),
+                                                  roots.p, bp, async ? &t : nullptr);
+        if (rc == RBC_OK && async && t) EXPECT(rbc_wait(ctx, t) == RBC_OK);  // before `out` goes
+        if (rc == RBC_OK)
+            for (int i = 0; i < count; ++i) EXPECT(slens[i] == (vl[i] + g.k - 1) / g.k);
+    } else {
+        const size_t need = (std::max(rbc_val_message_size(g.n, (uint32_t)Smax, 0, RBC_MSG_VAL),
+                                      rbc_val_message_size(g.n, (uint32_t)Smax, (uint32_t)(g.n - 1), RBC_MSG_VAL)) +
+                             15) / 16 * 16;
+        const size_t pitch = coin(85) ? need + 16 * rnd(3) : (coin(50) ? need - 16 : need + 1 + rnd(15));
+        bad_pitch = pitch < need || pitch % 16;
+        Buf msgs((size_t)count * g.n * pitch, coin(50)), mlens((size_t)count * g.n * 4, coin(50));
+        rc = rbc_shard_commit_val(ctx, count, vp.data(), vl.data(), msgs.p, pitch, (uint32_t *)mlens.p,
+                                  coin(30) ? nullptr : roots.p, async ? &t : nullptr);
+        if (rc == RBC_OK && async && t) EXPECT(rbc_wait(ctx, t) == RBC_OK);
+    }
     if (count > 0 && empty) EXPECT(rc == RBC_ERR_SHORT_DATA || rc == RBC_ERR_INVALID_ARG);
-    if (rc == RBC_OK && async && t) EXPECT(rbc_wait(g.ctx, t) == RBC_OK);
+    else if (count > 0 && bad_pitch) EXPECT(rc == RBC_ERR_INVALID_ARG);
+    else EXPECT(rc == RBC_OK);
+    if (fresh) rbc_ctx_destroy(ctx);
 }
 
 static void fuzz_interpolate_batch(Geo &g) {

@@ -213,8 +213,13 @@ hipError_t rbc_launch_gf_rows(const GfArgs &a, hipStream_t) {
         const uint8_t *oi = a.out_idx ? a.out_idx + (size_t)i * a.idx_stride2 : nullptr;
         for (int r = 0; r < a.R; ++r) {
             const uint32_t pos = oi ? oi[r] : (uint32_t)(a.K + r);
-            touch(a.out + (size_t)i * a.out_inst_pitch + (size_t)pos * a.out_row_pitch, a.out_row_pitch);
+            if (a.parity)  // encode into the dense arena
+                touch(a.parity + (size_t)i * a.parity_inst_pitch + (size_t)r * a.out_row_pitch, a.out_row_pitch);
+            else
+                touch(a.out + (size_t)i * a.out_inst_pitch + (size_t)pos * a.out_row_pitch, a.out_row_pitch);
         }
+        if (a.copy)  // encode: the data rows
+            touch(a.copy + (size_t)i * a.out_inst_pitch, (size_t)a.K * a.out_row_pitch);
         if (a.in_idx) peek(a.in_idx, (size_t)i * a.idx_stride + (a.K - 1));
         if (a.coef) peek(a.coef, (size_t)i * a.coef_inst_stride + (size_t)a.R * a.K - 1);
     }
@@ -226,12 +231,14 @@ hipError_t rbc_launch_gf_regen(const GfArgs &a, hipStream_t st) {
 }
 hipError_t rbc_launch_rs_fft(const FftArgs &a, hipStream_t) {
     if (a.count > 0) touch(a.shards, (size_t)a.count * a.inst_pitch);
+    if (a.count > 0 && a.mode == GF_MODE_ENCODE_PARITY) touch(a.parity, (size_t)a.count * a.parity_inst_pitch);
     if (a.count > 0 && a.join) touch(a.join, (size_t)a.count * a.join_pitch);  // the fused value join
     return hipSuccess;
 }
 hipError_t rbc_launch_sha_rows(const ShaArgs &a, bool verify, hipStream_t) {
     if (a.count <= 0) return hipSuccess;
-    if (a.leaves && !a.list && !a.per_message) touch(a.leaves, (size_t)a.count * a.leaves_inst_pitch);
+    if (a.leaves && !a.list && !a.per_message)  // slot s of instance i: leaves + i * pitch + 32 s
+        for (int i = 0; i < a.count; ++i) touch(a.leaves + (size_t)i * a.leaves_inst_pitch, (size_t)a.rows_per_inst * 32);
     if (a.leaves && a.per_message) touch(a.leaves, (size_t)a.count * 32);
     if (verify && a.valid) touch(a.valid, (size_t)a.count * (a.per_message ? 1 : a.n));
     return hipSuccess;

@@ -53,14 +53,15 @@ def _ctx(gpu, n, f, codec="auto"):
     return ctx
 
 
-def _check_batch(ctx, n, f, lens, out):
-    """out of shard_commit_parity_*: parity rows, lengths, roots and branches against the oracle."""
-    k = ctx.k
+def _check_batch(ctx, n, f, lens, out, key="parity", first=None):
+    """out of shard_commit_parity_* (or, key "shards" and first 0, shard_commit_*): the rows
+    `first` .. n-1, lengths, roots and branches against the oracle."""
+    first = ctx.k if first is None else first
     for i, B in enumerate(lens):
         shards, root, br, _ = _oracle(n, f, B)
         S = shards.shape[1]
         assert out["shard_lens"][i] == S
-        assert np.array_equal(out["parity"][i, :, :S], shards[k:]), (n, f, B)
+        assert np.array_equal(out[key][i, :, :S], shards[first:]), (n, f, B)
         assert bytes(out["roots"][i]) == root, (n, f, B)
         assert np.array_equal(out["branches"][i], br), (n, f, B)
 
@@ -88,33 +89,40 @@ def test_parity_rows_roots_and_branches_equal_the_oracle(gpu, n, f, codec):
 # ---- 2. the three output forms
 
 
-@pytest.mark.parametrize("form", ["pinned_flat", "pinned_odd_pitch", "pageable"])
-@pytest.mark.parametrize("n,f", [(128, 42), (37, 12)])
-def test_output_forms_and_nothing_written_past_the_output(gpu, n, f, form):
+# both commits share one output plan: the parity-only one keeps its case names
+FORM_CASES = [(entry, n, f, form) for entry in ("parity", "shards") for n, f in [(128, 42), (37, 12)]
+              for form in ["pinned_flat", "pinned_odd_pitch", "pageable"]]
+
+
+@pytest.mark.parametrize("entry,n,f,form", FORM_CASES,
+                         ids=[("" if e == "parity" else "full-") + f"{n}-{f}-{form}" for e, n, f, form in FORM_CASES])
+def test_output_forms_and_nothing_written_past_the_output(gpu, entry, n, f, form):
     ctx = _ctx(gpu, n, f)
-    k, p, d = ctx.k, ctx.p, ctx.depth
+    k, d = ctx.k, ctx.depth
+    rows, first = (ctx.p, k) if entry == "parity" else (n, 0)  # the rows handed back: shards first .. n-1
     lens = ragged_lens(k)
     count, Smax = len(lens), max((B + k - 1) // k for B in lens)
     pitch = {"pinned_flat": rup(Smax, 64), "pinned_odd_pitch": Smax + 3, "pageable": Smax}[form]
     alloc = (lambda shape: np.empty(shape, np.uint8)) if form == "pageable" else gpu.pinned_empty
-    raw = alloc(count * p * pitch + 64)
+    raw = alloc(count * rows * pitch + 64)
     raw[:] = 0xA5
-    out = {"parity": raw[: count * p * pitch].reshape(count, p, pitch), "roots": alloc((count, 32)),
+    out = {entry: raw[: count * rows * pitch].reshape(count, rows, pitch), "roots": alloc((count, 32)),
            "branches": alloc((count, n, d, 32))}
-    res = ctx.shard_commit_parity_submit([_value(n, f, B) for B in lens], out=out).wait()
-    _check_batch(ctx, n, f, lens, res)
-    assert (raw[count * p * pitch:] == 0xA5).all(), "sentinel after parity_out overwritten"
-    par = out["parity"]
+    submit = ctx.shard_commit_parity_submit if entry == "parity" else ctx.shard_commit_submit
+    res = submit([_value(n, f, B) for B in lens], out=out).wait()
+    _check_batch(ctx, n, f, lens, res, entry, first)
+    assert (raw[count * rows * pitch:] == 0xA5).all(), "sentinel after the output overwritten"
+    got = out[entry]
     for i, B in enumerate(lens):
         S = (B + k - 1) // k
         if form == "pinned_flat":  # ONE linear copy: whole rows, bytes [S_i, pitch) zero
-            assert not par[i, :, S:].any()
+            assert not got[i, :, S:].any()
         else:  # Smax bytes per row (zero past S_i); the bytes of the pitch beyond Smax are not touched
-            assert not par[i, :, S:Smax].any()
-            assert (par[i, :, Smax:] == 0xA5).all()
-        if S >= 16:  # data rows appear nowhere in the output
+            assert not got[i, :, S:Smax].any()
+            assert (got[i, :, Smax:] == 0xA5).all()
+        if entry == "parity" and S >= 16:  # data rows appear nowhere in the output
             data = {bytes(r) for r in _oracle(n, f, B)[0][:k]}
-            assert not any(bytes(par[i, r, :S]) in data for r in range(p))
+            assert not any(bytes(got[i, r, :S]) in data for r in range(rows))
 
 
 # ---- 3. reassembly and round trip
