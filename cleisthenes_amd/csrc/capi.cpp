@@ -216,6 +216,8 @@ int ctx_create_kn(int n, int k, int device, rbc_ctx **out) {
     if (!out) return RBC_ERR_INVALID_ARG;
     *out = nullptr;
     if (k <= 0 || n - k < 0) return RBC_ERR_INV_SHARD_NUM;
+    // so n <= 256 and the tree width <= 256 in every context: the stages never test either (a row
+    // position is one byte of a list entry, merkle_path_kernel and merkle_recheck_kernel take W <= 256)
     if (n > 256) return RBC_ERR_MAX_SHARD_NUM;
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev) return RBC_ERR_DEVICE;
@@ -267,14 +269,69 @@ hipStream_t aux_stream(Ws &w) {
 // or (split, rbc_dev_shard_commit_parity) the k data rows in rows
 // [count][k][pitch] and the p parity rows in the dense arena parity
 // [count][p][pitch].
+// With the rows' lengths (S_i per instance on the device, or one uniform
+// length) it is the one description of a shard batch every stage but the
+// encode takes; the encode is what decides them and does not read them.
 struct Rows {
     uint8_t *rows;
     uint32_t pitch;
+    const uint32_t *lens = nullptr;  // S_i, or NULL: uniform_len
+    uint32_t uniform_len = 0;
     bool split = false;
     uint8_t *parity = nullptr;
     // a buffer the form needs is NULL
     bool missing(const rbc_ctx *c) const { return !rows || (split && c->p > 0 && !parity); }
+    uint64_t inst_pitch(const rbc_ctx *c) const { return (uint64_t)(split ? c->k : c->n) * pitch; }
+    // the pitch keeps rows 64-byte aligned and holds a uniform row (per-instance lengths are device data)
+    bool rows_ok() const { return pitch % kAlign == 0 && (lens || (uniform_len > 0 && uniform_len <= pitch)); }
+    // ... and for the decode: an instance of less than 2^31 bytes, a value row
+    // (values_out NULL: the row view, no value) of whole 16-byte chunks that holds k uniform rows
+    bool decode_ok(const rbc_ctx *c, const uint8_t *values_out, uint32_t value_pitch) const {
+        return rows_ok() && (uint64_t)c->n * pitch <= 0x7fffffffULL &&
+               (!values_out || (value_pitch % 16 == 0 && (lens || value_pitch >= (uint64_t)uniform_len * c->k)));
+    }
 };
+
+// The row hashing over a batch (sha_rows_kernel, sha_rx_kernel): the batch's
+// geometry, leaves [count][n][32], the tree's n and depth, the wave priority.
+// The caller adds the row slots per instance, a list, the verify fields.
+ShaArgs sha_args(const rbc_ctx *c, int count, const Rows &b, uint8_t *leaves, int prio) {
+    ShaArgs a{};
+    a.count = count;
+    a.rows = b.rows;
+    a.inst_pitch = b.inst_pitch(c);
+    a.row_pitch = b.pitch;
+    a.lens = b.lens;
+    a.uniform_len = b.uniform_len;
+    a.leaves = leaves;
+    a.leaves_inst_pitch = (uint64_t)c->n * 32;
+    a.n = c->n;
+    a.depth = c->depth;
+    a.prio = prio;
+    return a;
+}
+
+// The head the tree build and the root recheck share (merkle_kernel)
+MerkleArgs merkle_args(const rbc_ctx *c, int count, const uint8_t *leaves, int prio) {
+    MerkleArgs m{};
+    m.count = count;
+    m.n = c->n;
+    m.width = c->width;
+    m.depth = c->depth;
+    m.k = c->k;
+    m.leaves = leaves;
+    m.leaves_inst_pitch = (uint64_t)c->n * 32;
+    m.prio = prio;
+    return m;
+}
+// ... and the recheck's form: the roots recomputed and compared, status[i] in and out
+MerkleArgs merkle_check_args(const rbc_ctx *c, int count, const uint8_t *leaves, const uint8_t *roots,
+                             int32_t *status) {
+    MerkleArgs m = merkle_args(c, count, leaves, c->rx_prio);
+    m.expect_roots = roots;
+    m.status = status;
+    return m;
+}
 
 int stage_encode(rbc_ctx *c, hipStream_t st, int count, const uint8_t *values, uint64_t value_pitch,
                  const uint32_t *value_lens, uint32_t uniform_value_len, const Rows &out) {
@@ -287,7 +344,7 @@ int stage_encode(rbc_ctx *c, hipStream_t st, int count, const uint8_t *values, u
     }
     if (value_pitch > 0x7fffffffULL || (uint64_t)c->n * out.pitch > 0x7fffffffULL) return RBC_ERR_INVALID_ARG;
     if (count == 0) return RBC_OK;
-    const uint64_t inst_pitch = (uint64_t)(out.split ? c->k : c->n) * out.pitch;
+    const uint64_t inst_pitch = out.inst_pitch(c);
     const uint64_t parity_inst_pitch = out.split ? (uint64_t)c->p * out.pitch : 0;
     if (c->fft) {
         FftArgs a{};
@@ -336,25 +393,12 @@ int stage_encode(rbc_ctx *c, hipStream_t st, int count, const uint8_t *values, u
 // leaves [count][n][32] of the rows: one launch of the row hashing over the n
 // rows of one buffer, or (split) one over the k data rows and one over the p
 // arena rows -- each over a dense [count][rows][pitch] buffer.
-int stage_leaves(rbc_ctx *c, hipStream_t st, int count, const Rows &in, const uint32_t *shard_lens,
-                 uint32_t uniform_shard_len, uint8_t *leaves) {
+int stage_leaves(rbc_ctx *c, hipStream_t st, int count, const Rows &in, uint8_t *leaves) {
     if (count < 0 || (count > 0 && (in.missing(c) || !leaves))) return RBC_ERR_INVALID_ARG;
-    if (in.pitch % kAlign || (!shard_lens && (uniform_shard_len == 0 || uniform_shard_len > in.pitch)))
-        return RBC_ERR_INVALID_ARG;
+    if (!in.rows_ok()) return RBC_ERR_INVALID_ARG;
     if (count == 0) return RBC_OK;
-    ShaArgs a{};
-    a.count = count;
+    ShaArgs a = sha_args(c, count, in, leaves, c->tx_prio);
     a.rows_per_inst = in.split ? c->k : c->n;
-    a.rows = in.rows;
-    a.inst_pitch = (uint64_t)a.rows_per_inst * in.pitch;
-    a.row_pitch = in.pitch;
-    a.lens = shard_lens;
-    a.uniform_len = uniform_shard_len;
-    a.leaves = leaves;
-    a.leaves_inst_pitch = (uint64_t)c->n * 32;
-    a.n = c->n;
-    a.depth = c->depth;
-    a.prio = c->tx_prio;
     RBC_HIP(rbc_launch_sha_rows(a, false, st));
     if (in.split && c->p > 0) {
         a.rows_per_inst = c->p;
@@ -370,18 +414,10 @@ int stage_merkle_build(rbc_ctx *c, hipStream_t st, int count, const uint8_t *lea
                        uint8_t *branches) {
     if (count < 0 || (count > 0 && (!leaves || !roots))) return RBC_ERR_INVALID_ARG;
     if (count == 0) return RBC_OK;
-    MerkleArgs m{};
-    m.count = count;
-    m.n = c->n;
-    m.width = c->width;
-    m.depth = c->depth;
-    m.k = c->k;
-    m.leaves = leaves;
-    m.leaves_inst_pitch = (uint64_t)c->n * 32;
+    MerkleArgs m = merkle_args(c, count, leaves, c->tx_prio);
     m.roots = roots;
     m.branches = c->depth > 0 ? branches : nullptr;
     m.br_inst_pitch = (uint64_t)c->n * c->depth * 32;
-    m.prio = c->tx_prio;
     RBC_HIP(rbc_launch_merkle(m, false, st));
     return RBC_OK;
 }
@@ -392,8 +428,10 @@ int commit_stages(rbc_ctx *c, hipStream_t st, int count, const uint8_t *values, 
                   const uint32_t *shard_lens, uint8_t *leaves, uint8_t *roots, uint8_t *branches) {
     int rc = stage_encode(c, st, count, values, value_pitch, value_lens, uniform_value_len, rows);
     if (rc) return rc;
-    const uint32_t uS = value_lens ? 0u : (uniform_value_len + c->k - 1) / c->k;
-    rc = stage_leaves(c, st, count, rows, shard_lens, uS, leaves);
+    Rows made = rows;  // with the lengths the encode gave them
+    made.lens = shard_lens;
+    made.uniform_len = value_lens ? 0u : (uniform_value_len + c->k - 1) / c->k;
+    rc = stage_leaves(c, st, count, made, leaves);
     if (rc) return rc;
     return stage_merkle_build(c, st, count, leaves, roots, branches);
 }
@@ -404,92 +442,103 @@ int commit_stages(rbc_ctx *c, hipStream_t st, int count, const uint8_t *values, 
 // walk fused into the row hashing where they are not (C2: 14 vs 373).
 static bool shared_path_verify(const rbc_ctx *c, const uint32_t *shard_lens, uint32_t uniform_shard_len) {
     const uint32_t blocks_per_row = shard_lens ? 0u : (uniform_shard_len + 9 + 63) / 64;
-    return (shard_lens || 16u * (uint32_t)c->depth >= blocks_per_row) && c->depth >= 1 && c->width <= 256;
+    return (shard_lens || 16u * (uint32_t)c->depth >= blocks_per_row) && c->depth >= 1;
 }
 
-// wsp: a host-API slot's own workspace (its submission already holds c->mu);
-// NULL: the context's, guarded by c->mu here (device API)
-int stage_verify(rbc_ctx *c, hipStream_t st, int count, const uint8_t *shards, uint32_t shard_pitch,
-                 const uint32_t *shard_lens, uint32_t uniform_shard_len, const uint8_t *branches,
-                 const uint8_t *roots, const uint8_t *present, uint8_t *valid, uint8_t *leaves, Ws *wsp = nullptr) {
-    if (count < 0 || (count > 0 && (!shards || !roots || !valid || (c->depth > 0 && !branches))))
-        return RBC_ERR_INVALID_ARG;
-    if (shard_pitch % kAlign || (!shard_lens && (uniform_shard_len == 0 || uniform_shard_len > shard_pitch)))
-        return RBC_ERR_INVALID_ARG;
-    if (count == 0) return RBC_OK;
-    ShaArgs a{};
-    a.count = count;
-    a.rows_per_inst = c->n;
-    a.rows = shards;
-    a.inst_pitch = (uint64_t)c->n * shard_pitch;
-    a.row_pitch = shard_pitch;
-    a.lens = shard_lens;
-    a.uniform_len = uniform_shard_len;
-    a.leaves = leaves;
-    a.leaves_inst_pitch = (uint64_t)c->n * 32;
-    a.n = c->n;
-    a.depth = c->depth;
-    a.branches = branches;
-    a.br_inst_pitch = (uint64_t)c->n * c->depth * 32;
-    a.roots = roots;
-    a.present = present;
-    a.valid = valid;
-    a.prio = c->rx_prio;
-    // Shared-path verification: leaves, then one hash per
-    // distinct branch-walk input.
-    // The per-leaf walk costs 2d compressions per row on top of the leaf's
-    // ceil((S+9)/64); the shared-path form pays off where that walk is a real
-    // share (C4: 16 vs 13) and only adds a launch where it is not (C2: 14 vs
-    // 373, measured equal alone and slower beside a second stream).
-    const bool path_pays = shared_path_verify(c, shard_lens, uniform_shard_len);
-    // Only the received ECHOs are validated (validateMessage runs per message):
-    // with a present mask the shards to hash are compacted into a device list
-    // first (N-f of N in the bench: a third fewer SHA rows than hashing all N).
-    if (present && c->n <= 256) {
-        uint32_t *vl = nullptr, *vc = nullptr;
-        {
-            std::unique_lock<std::mutex> lk(c->mu, std::defer_lock);
-            if (!wsp) lk.lock();
-            Ws &w = wsp ? *wsp : c->ws;
-            RBC_HIP(w.vlist.ensure((size_t)count * c->n * 4 + 64));
-            vl = w.vlist.as<uint32_t>();
-            vc = vl + (size_t)count * c->n;
+// A workspace buffer of at least `bytes` for a stage (NULL: no memory).  wsp:
+// the workspace is the caller's to use -- a host-API slot's own (its submission
+// already holds c->mu) or the context's with c->mu held (the receive step);
+// NULL: the context's, guarded by c->mu here for the ensure only (device API)
+void *ws_buffer(rbc_ctx *c, Ws *wsp, DevBuf Ws::*buf, size_t bytes) {
+    std::unique_lock<std::mutex> lk(c->mu, std::defer_lock);
+    if (!wsp) lk.lock();
+    Ws &w = wsp ? *wsp : c->ws;
+    DevBuf &b = w.*buf;
+    return b.ensure(bytes) == hipSuccess ? b.p : nullptr;
+}
+
+// ECHO verify of one batch, shared by stage_verify (which hashes with
+// sha_rows) and the receive step (sha_rx, beside prev's regen rows).  plan()
+// builds the hashing's arguments, compacts the present rows and picks the
+// form; the caller launches `sha` (with the walk unless `path`), then finish().
+struct EchoVerify {
+    // the receive step's own list counter (NULL: the word behind the list),
+    // whether it still has to be zeroed here, and where the compaction copies
+    // the batch's roots on its way (NULL: no copy)
+    uint32_t *counter = nullptr;
+    bool zero_counter = true;
+    uint8_t *roots_keep = nullptr;
+    ShaArgs sha{};
+    bool path = false;  // leaves by the hashing, then merkle_path_kernel; else the walk fused into the hashing
+
+    int plan(rbc_ctx *c, hipStream_t st, int count, const Rows &b, const uint8_t *branches, const uint8_t *roots,
+             const uint8_t *present, uint8_t *valid, uint8_t *leaves, Ws *wsp) {
+        sha = sha_args(c, count, b, leaves, c->rx_prio);
+        sha.rows_per_inst = c->n;
+        sha.branches = branches;
+        sha.br_inst_pitch = (uint64_t)c->n * c->depth * 32;
+        sha.roots = roots;
+        sha.present = present;
+        sha.valid = valid;
+        // Only the received ECHOs are validated (validateMessage runs per message):
+        // with a present mask the shards to hash are compacted into a device list
+        // first (N-f of N in the bench: a third fewer SHA rows than hashing all N).
+        if (present) {
+            uint32_t *vl = (uint32_t *)ws_buffer(c, wsp, &Ws::vlist, (size_t)count * c->n * 4 + 64);
+            if (!vl) return RBC_ERR_DEVICE;
+            uint32_t *vc = counter ? counter : vl + (size_t)count * c->n;
+            if (zero_counter) RBC_HIP(hipMemsetAsync(vc, 0, 4, st));
+            RBC_HIP(rbc_launch_compact_present(present, c->n, count, valid, vl, vc, st, c->rx_prio,
+                                               roots_keep ? roots : nullptr, roots_keep));
+            sha.list = vl;
+            sha.list_count = vc;
         }
-        RBC_HIP(hipMemsetAsync(vc, 0, 4, st));
-        RBC_HIP(rbc_launch_compact_present(present, c->n, count, valid, vl, vc, st, c->rx_prio));
-        a.list = vl;
-        a.list_count = vc;
+        // Shared-path verification: leaves, then one hash per
+        // distinct branch-walk input.
+        // The per-leaf walk costs 2d compressions per row on top of the leaf's
+        // ceil((S+9)/64); the shared-path form pays off where that walk is a real
+        // share (C4: 16 vs 13) and only adds a launch where it is not (C2: 14 vs
+        // 373, measured equal alone and slower beside a second stream).
+        path = shared_path_verify(c, b.lens, b.uniform_len);
+        if (path && !leaves) {
+            sha.leaves = (uint8_t *)ws_buffer(c, wsp, &Ws::vleaves, (size_t)count * c->n * 32);
+            if (!sha.leaves) return RBC_ERR_DEVICE;
+        }
+        return RBC_OK;
     }
-    if (path_pays) {
-        uint8_t *lv = leaves;
-        if (!lv) {
-            std::unique_lock<std::mutex> lk(c->mu, std::defer_lock);
-            if (!wsp) lk.lock();
-            Ws &w = wsp ? *wsp : c->ws;
-            RBC_HIP(w.vleaves.ensure((size_t)count * c->n * 32));
-            lv = w.vleaves.as<uint8_t>();
-        }
-        a.leaves = lv;
-        RBC_HIP(rbc_launch_sha_rows(a, false, st));
+    int finish(const rbc_ctx *c, hipStream_t st) const {
+        if (!path) return RBC_OK;
         PathArgs p{};
-        p.count = count;
+        p.count = sha.count;
         p.n = c->n;
         p.width = c->width;
         p.lg_width = c->depth;
         p.depth = c->depth;
-        p.leaves = lv;
-        p.leaves_inst_pitch = (uint64_t)c->n * 32;
-        p.branches = branches;
-        p.br_inst_pitch = (uint64_t)c->n * c->depth * 32;
-        p.roots = roots;
-        p.present = present;
-        p.valid = valid;
-        p.prio = c->rx_prio;
+        p.leaves = sha.leaves;
+        p.leaves_inst_pitch = sha.leaves_inst_pitch;
+        p.branches = sha.branches;
+        p.br_inst_pitch = sha.br_inst_pitch;
+        p.roots = sha.roots;
+        p.present = sha.present;
+        p.valid = sha.valid;
+        p.prio = sha.prio;
         RBC_HIP(rbc_launch_merkle_path(p, st));
         return RBC_OK;
     }
-    RBC_HIP(rbc_launch_sha_rows(a, true, st));
-    return RBC_OK;
+};
+
+// wsp: as ws_buffer
+int stage_verify(rbc_ctx *c, hipStream_t st, int count, const Rows &b, const uint8_t *branches, const uint8_t *roots,
+                 const uint8_t *present, uint8_t *valid, uint8_t *leaves, Ws *wsp = nullptr) {
+    if (count < 0 || (count > 0 && (!b.rows || !roots || !valid || (c->depth > 0 && !branches))))
+        return RBC_ERR_INVALID_ARG;
+    if (!b.rows_ok()) return RBC_ERR_INVALID_ARG;
+    if (count == 0) return RBC_OK;
+    EchoVerify ev;
+    int rc = ev.plan(c, st, count, b, branches, roots, present, valid, leaves, wsp);
+    if (rc) return rc;
+    RBC_HIP(rbc_launch_sha_rows(ev.sha, !ev.path, st));
+    return ev.finish(c, st);
 }
 
 int ensure_ws(rbc_ctx *c, Ws &w, int count) {
@@ -506,6 +555,33 @@ int ensure_ws(rbc_ctx *c, Ws &w, int count) {
     return RBC_OK;
 }
 
+// The decode's GF product (gf_regen_kernel, gf_rows_kernel): the batch's rows
+// in place, decode_prepare's matrix and row positions.  The caller adds the
+// output row count, its kernel's tiling, the compare fields and the priority.
+GfArgs decode_gf_args(const rbc_ctx *c, int count, const Rows &b, const PrepArgs &pa) {
+    GfArgs g{};
+    g.count = count;
+    g.K = c->k;
+    g.mode = GF_MODE_DECODE;
+    g.in = b.rows;
+    g.in_inst_pitch = b.inst_pitch(c);
+    g.in_row_pitch = b.pitch;
+    g.in_inst_bytes = (uint32_t)b.inst_pitch(c);
+    g.out = b.rows;
+    g.out_inst_pitch = b.inst_pitch(c);
+    g.out_row_pitch = b.pitch;
+    g.lens = b.lens;
+    g.uniform_len = b.uniform_len;
+    g.coef = pa.dmat;
+    g.coef_inst_stride = pa.dmat_stride;
+    g.in_idx = pa.used;
+    g.out_idx = pa.regen;
+    g.idx_stride = pa.used_stride;
+    g.idx_stride2 = pa.regen_stride;
+    g.status = pa.status;
+    return g;
+}
+
 // decode_prepare + GF regeneration (in place), no hashing
 // compare != 0: valid-but-unused rows are compared, not blindly rewritten,
 // and the rows that need hashing are collected in ws_list
@@ -519,8 +595,7 @@ int ensure_ws(rbc_ctx *c, Ws &w, int count) {
 // stream, beside the recheck: C4 349 -> 361 GB/s, while C1 / C2 lose 4 % that
 // way (profiles/r06am/).
 constexpr uint32_t kFusedJoinMinS = 2048;
-int stage_regenerate(rbc_ctx *c, Ws &w, hipStream_t st, int count, uint8_t *shards, uint32_t shard_pitch,
-                     const uint32_t *shard_lens, uint32_t uniform_shard_len, const uint8_t *valid,
+int stage_regenerate(rbc_ctx *c, Ws &w, hipStream_t st, int count, const Rows &b, const uint8_t *valid,
                      int32_t *status, int compare = 0, uint32_t *zeroed_counter = nullptr,
                      uint8_t *values_out = nullptr, uint32_t value_pitch = 0, bool *joined = nullptr) {
     if (joined) *joined = false;
@@ -564,28 +639,10 @@ int stage_regenerate(rbc_ctx *c, Ws &w, hipStream_t st, int count, uint8_t *shar
     if (c->fft && nr > 0) {
         // 1) missing data rows: D (rcount[i] x k, per instance) times the used rows
         const int rmax = std::min(c->k, nr);
-        GfArgs g{};
-        g.count = count;
+        // (gf_regen_kernel's column tiles and block shape: rbc_launch_gf_regen, gf_regen.hip;
+        // no compare here, the re-encode below compares)
+        GfArgs g = decode_gf_args(c, count, b, pa);
         g.R = rmax;
-        g.K = c->k;
-        // gf_regen_kernel's column tiles and block shape: rbc_launch_gf_regen (gf_regen.hip)
-        g.mode = GF_MODE_DECODE;
-        g.in = shards;
-        g.in_inst_pitch = (uint64_t)c->n * shard_pitch;
-        g.in_row_pitch = shard_pitch;
-        g.in_inst_bytes = (uint32_t)((uint64_t)c->n * shard_pitch);
-        g.out = shards;
-        g.out_inst_pitch = (uint64_t)c->n * shard_pitch;
-        g.out_row_pitch = shard_pitch;
-        g.lens = shard_lens;
-        g.uniform_len = uniform_shard_len;
-        g.coef = pa.dmat;
-        g.coef_inst_stride = pa.dmat_stride;
-        g.in_idx = pa.used;
-        g.out_idx = pa.regen;
-        g.idx_stride = pa.used_stride;
-        g.idx_stride2 = pa.regen_stride;
-        g.status = status;
         g.rcount = pa.rcount;
         g.prio = c->gemv_prio();
         RBC_HIP(rbc_launch_gf_regen(g, st));
@@ -595,11 +652,11 @@ int stage_regenerate(rbc_ctx *c, Ws &w, hipStream_t st, int count, uint8_t *shar
         a.n = c->n;
         a.k = c->k;
         a.mode = GF_MODE_DECODE;
-        a.shards = shards;
-        a.inst_pitch = (uint64_t)c->n * shard_pitch;
-        a.row_pitch = shard_pitch;
-        a.lens = shard_lens;
-        a.uniform_len = uniform_shard_len;
+        a.shards = b.rows;
+        a.inst_pitch = b.inst_pitch(c);
+        a.row_pitch = b.pitch;
+        a.lens = b.lens;
+        a.uniform_len = b.uniform_len;
         a.status = status;
         a.cls = pa.cls;
         a.cls_stride = pa.cls_stride;
@@ -612,39 +669,19 @@ int stage_regenerate(rbc_ctx *c, Ws &w, hipStream_t st, int count, uint8_t *shar
         // tile 0's lanes zero the value's tail, 4 B each, and only the lanes
         // with a column inside the row pitch run (rs_fft.hip): the tail must
         // fit min(256, shard_pitch) bytes, else the separate join zero-fills it
-        if (values_out && joined && !shard_lens && uniform_shard_len >= kFusedJoinMinS &&
-            value_pitch >= (uint64_t)c->k * uniform_shard_len &&
-            value_pitch - (uint64_t)c->k * uniform_shard_len <= std::min<uint64_t>(256, shard_pitch)) {
+        if (values_out && joined && !b.lens && b.uniform_len >= kFusedJoinMinS &&
+            value_pitch >= (uint64_t)c->k * b.uniform_len &&
+            value_pitch - (uint64_t)c->k * b.uniform_len <= std::min<uint64_t>(256, b.pitch)) {
             a.join = values_out;
             a.join_pitch = value_pitch;
             *joined = true;
         }
         RBC_HIP(rbc_launch_rs_fft(a, st));
     } else if (nr > 0) {
-        GfArgs g{};
-        g.count = count;
-        g.tiles = (int)((shard_pitch + 4095) / 4096);
+        GfArgs g = decode_gf_args(c, count, b, pa);  // in place: no `copy` of the used rows
+        g.tiles = (int)((b.pitch + 4095) / 4096);
         g.R = nr;
-        g.K = c->k;
         g.rc = rbc_gf_pick_rc(nr, kGfRcMax);
-        g.mode = GF_MODE_DECODE;
-        g.in = shards;
-        g.in_inst_pitch = (uint64_t)c->n * shard_pitch;
-        g.in_row_pitch = shard_pitch;
-        g.in_inst_bytes = (uint32_t)((uint64_t)c->n * shard_pitch);
-        g.out = shards;
-        g.out_inst_pitch = (uint64_t)c->n * shard_pitch;
-        g.out_row_pitch = shard_pitch;
-        g.copy = nullptr;
-        g.lens = shard_lens;
-        g.uniform_len = uniform_shard_len;
-        g.coef = pa.dmat;
-        g.coef_inst_stride = pa.dmat_stride;
-        g.in_idx = pa.used;
-        g.out_idx = pa.regen;
-        g.idx_stride = pa.used_stride;
-        g.idx_stride2 = pa.regen_stride;
-        g.status = status;
         if (compare) {
             g.nmiss = pa.nmiss;
             g.flags = pa.flags;
@@ -665,26 +702,26 @@ struct JoinBack {
     Ws &w;
     hipStream_t st;
     bool armed = false;
+    bool record = true;  // false: the caller recorded ev_join on the aux stream itself (the receive step)
     ~JoinBack() {
         if (!armed) return;
-        (void)hipEventRecord(w.ev_join, w.aux);
+        if (record) (void)hipEventRecord(w.ev_join, w.aux);
         (void)hipStreamWaitEvent(st, w.ev_join, 0);
     }
 };
 
-int launch_join(rbc_ctx *c, hipStream_t js, int count, const uint8_t *shards, uint32_t shard_pitch,
-                const uint32_t *shard_lens, uint32_t uniform_shard_len, uint8_t *values_out, uint32_t value_pitch,
+int launch_join(rbc_ctx *c, hipStream_t js, int count, const Rows &b, uint8_t *values_out, uint32_t value_pitch,
                 const int32_t *status) {
     JoinArgs j{};
     j.count = count;
     j.k = c->k;
     j.chunks = value_pitch / 16;
-    j.shards = shards;
-    j.inst_pitch = (uint64_t)c->n * shard_pitch;
-    j.row_pitch = shard_pitch;
-    j.inst_bytes = (uint32_t)((uint64_t)c->n * shard_pitch);
-    j.lens = shard_lens;
-    j.uniform_len = uniform_shard_len;
+    j.shards = b.rows;
+    j.inst_pitch = b.inst_pitch(c);
+    j.row_pitch = b.pitch;
+    j.inst_bytes = (uint32_t)b.inst_pitch(c);
+    j.lens = b.lens;
+    j.uniform_len = b.uniform_len;
     j.values = values_out;
     j.value_pitch = value_pitch;
     j.status = status;
@@ -699,21 +736,16 @@ int launch_join(rbc_ctx *c, hipStream_t js, int count, const uint8_t *shards, ui
 // k data rows of `shards` (regenerated in place).  With w.fork the join
 // (HBM-bound) runs on the aux stream beside the rehash (latency-bound, it
 // under-fills the SIMDs) and the digest beside the recheck.
-int stage_interpolate(rbc_ctx *c, Ws &w, hipStream_t st, int count, uint8_t *shards, uint32_t shard_pitch,
-                      const uint32_t *shard_lens, uint32_t uniform_shard_len, const uint8_t *valid, uint8_t *leaves,
-                      int leaves_verified, const uint8_t *roots, uint8_t *values_out, uint32_t value_pitch,
-                      uint8_t *digests, int32_t *status) {
-    if (count < 0 || (count > 0 && (!shards || !valid || !leaves || !roots || !status)))
+int stage_interpolate(rbc_ctx *c, Ws &w, hipStream_t st, int count, const Rows &b, const uint8_t *valid,
+                      uint8_t *leaves, int leaves_verified, const uint8_t *roots, uint8_t *values_out,
+                      uint32_t value_pitch, uint8_t *digests, int32_t *status) {
+    if (count < 0 || (count > 0 && (!b.rows || !valid || !leaves || !roots || !status)))
         return RBC_ERR_INVALID_ARG;
-    if (shard_pitch % kAlign || (values_out && value_pitch % 16)) return RBC_ERR_INVALID_ARG;
-    if (!shard_lens && (uniform_shard_len == 0 || uniform_shard_len > shard_pitch ||
-                        (values_out && value_pitch < (uint64_t)uniform_shard_len * c->k)))
-        return RBC_ERR_INVALID_ARG;
-    if ((uint64_t)c->n * shard_pitch > 0x7fffffffULL) return RBC_ERR_INVALID_ARG;
+    if (!b.decode_ok(c, values_out, value_pitch)) return RBC_ERR_INVALID_ARG;
     if (count == 0) return RBC_OK;
     bool joined = false;
-    int rc = stage_regenerate(c, w, st, count, shards, shard_pitch, shard_lens, uniform_shard_len, valid, status,
-                              leaves_verified, nullptr, values_out, value_pitch, &joined);
+    int rc = stage_regenerate(c, w, st, count, b, valid, status, leaves_verified, nullptr, values_out, value_pitch,
+                              &joined);
     if (rc) return rc;
     JoinBack jb{w, st};
     if (w.fork && (values_out || digests) && !aux_stream(w)) return RBC_ERR_DEVICE;
@@ -725,24 +757,12 @@ int stage_interpolate(rbc_ctx *c, Ws &w, hipStream_t st, int count, uint8_t *sha
             jb.armed = true;
             js = w.aux;
         }
-        rc = launch_join(c, js, count, shards, shard_pitch, shard_lens, uniform_shard_len, values_out, value_pitch,
-                         status);
+        rc = launch_join(c, js, count, b, values_out, value_pitch, status);
         if (rc) return rc;
     }
     const int nr = c->n - c->k;
-    ShaArgs a{};
-    a.count = count;
-    a.rows = shards;
-    a.inst_pitch = (uint64_t)c->n * shard_pitch;
-    a.row_pitch = shard_pitch;
-    a.lens = shard_lens;
-    a.uniform_len = uniform_shard_len;
+    ShaArgs a = sha_args(c, count, b, leaves, c->rx_prio);
     a.status = status;
-    a.leaves = leaves;
-    a.leaves_inst_pitch = (uint64_t)c->n * 32;
-    a.n = c->n;
-    a.depth = c->depth;
-    a.prio = c->rx_prio;
     if (leaves_verified) {
         // hash only the rows in the device-built list: every missing position
         // plus any valid-but-unused shard the re-encoding disagreed with
@@ -753,17 +773,7 @@ int stage_interpolate(rbc_ctx *c, Ws &w, hipStream_t st, int count, uint8_t *sha
         a.rows_per_inst = c->n;
     }
     if (a.rows_per_inst > 0) RBC_HIP(rbc_launch_sha_rows(a, false, st));
-    MerkleArgs m{};
-    m.count = count;
-    m.n = c->n;
-    m.width = c->width;
-    m.depth = c->depth;
-    m.k = c->k;
-    m.leaves = leaves;
-    m.leaves_inst_pitch = (uint64_t)c->n * 32;
-    m.expect_roots = roots;
-    m.status = status;
-    m.prio = c->rx_prio;
+    const MerkleArgs m = merkle_check_args(c, count, leaves, roots, status);
     // the batch digest (one serial 23-compression chain per instance at C2)
     // needs only the data leaves: it runs on the aux stream beside the recheck
     hipStream_t ds = st;
@@ -784,17 +794,15 @@ int stage_interpolate(rbc_ctx *c, Ws &w, hipStream_t st, int count, uint8_t *sha
 // cur's decode.  The value join of cur runs on the aux stream and is waited
 // for by the next call (with prev's digest), so a batch is final when the
 // call that names it `prev` has run.
+Rows rx_rows(const rbc_rx_batch *b) { return {b->shards, b->shard_pitch, b->shard_lens, b->uniform_shard_len}; }
+
+// stage_interpolate's checks, and the branches ECHO verify needs
 int check_rx_batch(rbc_ctx *c, const rbc_rx_batch *b) {
     if (b->count < 0) return RBC_ERR_INVALID_ARG;
     if (b->count == 0) return RBC_OK;
     if (!b->shards || !b->roots || !b->valid || !b->leaves || !b->status || (c->depth > 0 && !b->branches))
         return RBC_ERR_INVALID_ARG;
-    if (b->shard_pitch % kAlign || (b->values_out && b->value_pitch % 16)) return RBC_ERR_INVALID_ARG;
-    if (!b->shard_lens && (b->uniform_shard_len == 0 || b->uniform_shard_len > b->shard_pitch ||
-                           (b->values_out && b->value_pitch < (uint64_t)b->uniform_shard_len * c->k)))
-        return RBC_ERR_INVALID_ARG;
-    if ((uint64_t)c->n * b->shard_pitch > 0x7fffffffULL) return RBC_ERR_INVALID_ARG;
-    return RBC_OK;
+    return rx_rows(b).decode_ok(c, b->values_out, b->value_pitch) ? RBC_OK : RBC_ERR_INVALID_ARG;
 }
 
 // cur and prev are both in flight during a call: no output buffer may be shared
@@ -818,9 +826,9 @@ int stage_receive_step(rbc_ctx *c, hipStream_t st, const rbc_rx_batch *cur, cons
     if (!hc && !hp) return RBC_OK;
     if (!aux_stream(w)) return RBC_ERR_DEVICE;
     const int nr = c->n - c->k;
-    ShaArgs v{}, r{};
-    v.prio = c->rx_prio;  // the launch's wave priority (also when only prev's rows are hashed)
-    bool v_walk = false, v_path = false;
+    EchoVerify ev;  // cur's ECHO verify, when this step still has to run it
+    ShaArgs r{};    // prev's regenerated rows
+    ev.sha.prio = c->rx_prio;  // the launch's wave priority (also when only prev's rows are hashed)
     // list counters: cur's compaction V[par], cur's regen list R[par], prev's
     // regen list R[par ^ 1] (its decode ran in the previous call, whose parity
     // was par ^ 1); the hashing launch zeroes R[par] and V[par ^ 1]
@@ -836,55 +844,28 @@ int stage_receive_step(rbc_ctx *c, hipStream_t st, const rbc_rx_batch *cur, cons
              *r_prev = cnt + 8 + 4 * (par ^ 1);
     // node-reuse recheck (merkle_recheck_kernel): keep the roots cur's branches
     // are verified against now, for cur's recheck in the next call
-    const bool reuse = c->recheck == RBC_RECHECK_REUSE && c->depth >= 1 && c->width <= 256;
+    const bool reuse = c->recheck == RBC_RECHECK_REUSE && c->depth >= 1;
     const int cur_vslot = w.rx_vslot ^ (hp ? 1 : 0);
     bool roots_kept = false;
     if (hc && reuse) RBC_HIP(w.vroot[cur_vslot].ensure((size_t)cur->count * 32));
     const bool hv = hc && !cur->verified;  // cur's ECHOs still to verify in this step
     if (hv) {
-        v.count = cur->count;
-        v.rows_per_inst = c->n;
-        v.rows = cur->shards;
-        v.inst_pitch = (uint64_t)c->n * cur->shard_pitch;
-        v.row_pitch = cur->shard_pitch;
-        v.lens = cur->shard_lens;
-        v.uniform_len = cur->uniform_shard_len;
-        v.leaves = cur->leaves;
-        v.leaves_inst_pitch = (uint64_t)c->n * 32;
-        v.n = c->n;
-        v.depth = c->depth;
-        v.branches = cur->branches;
-        v.br_inst_pitch = (uint64_t)c->n * c->depth * 32;
-        v.roots = cur->roots;
-        v.present = cur->present;
-        v.valid = cur->valid;
-        if (cur->present && c->n <= 256) {  // hash only the received shards (stage_verify)
-            RBC_HIP(w.vlist.ensure((size_t)cur->count * c->n * 4 + 64));
-            uint32_t *vl = w.vlist.as<uint32_t>();
-            if (!w.v_clean[par]) RBC_HIP(hipMemsetAsync(v_cnt, 0, 4, st));  // after an error or a one-shot call
-            RBC_HIP(rbc_launch_compact_present(cur->present, c->n, cur->count, cur->valid, vl, v_cnt, st, c->rx_prio,
-                                               reuse ? cur->roots : nullptr,
-                                               reuse ? w.vroot[cur_vslot].as<uint8_t>() : nullptr));
+        ev.counter = v_cnt;
+        ev.zero_counter = !w.v_clean[par];  // after an error or a one-shot call
+        ev.roots_keep = reuse ? w.vroot[cur_vslot].as<uint8_t>() : nullptr;
+        rc = ev.plan(c, st, cur->count, rx_rows(cur), cur->branches, cur->roots, cur->present, cur->valid, cur->leaves,
+                     &w);
+        if (rc) return rc;
+        if (cur->present) {  // the compaction ran: it used V[par] and carried the roots
             w.v_clean[par] = false;
             roots_kept = reuse;
-            v.list = vl;
-            v.list_count = v_cnt;
         }
-        // the shared-path verify where the branch walk is a real share (C4), as stage_verify
-        v_path = shared_path_verify(c, cur->shard_lens, cur->uniform_shard_len);
-        v_walk = !v_path;
     }
     if (hp && nr > 0) {
-        r.count = prev->count;
+        // (sha_rx_kernel reads neither n, depth nor prio of its r block)
+        r = sha_args(c, prev->count, rx_rows(prev), prev->leaves, c->rx_prio);
         r.rows_per_inst = nr;
-        r.rows = prev->shards;
-        r.inst_pitch = (uint64_t)c->n * prev->shard_pitch;
-        r.row_pitch = prev->shard_pitch;
-        r.lens = prev->shard_lens;
-        r.uniform_len = prev->uniform_shard_len;
         r.status = prev->status;
-        r.leaves = prev->leaves;
-        r.leaves_inst_pitch = (uint64_t)c->n * 32;
         r.list = w.list.as<uint32_t>();
         r.list_count = r_prev;
     }
@@ -893,37 +874,15 @@ int stage_receive_step(rbc_ctx *c, hipStream_t st, const rbc_rx_batch *cur, cons
     if (marks && marks->hash_begin) RBC_HIP(hipEventRecord((hipEvent_t)marks->hash_begin, st));
     // (a verified cur leaves only prev's regen rows; with neither side the
     // launch still zeroes the next users' counters)
-    RBC_HIP(rbc_launch_sha_rx(v, r, v_walk, st, reinterpret_cast<uint4 *>(r_cnt), reinterpret_cast<uint4 *>(v_next)));
+    RBC_HIP(rbc_launch_sha_rx(ev.sha, r, hv && !ev.path, st, reinterpret_cast<uint4 *>(r_cnt),
+                              reinterpret_cast<uint4 *>(v_next)));
     w.v_clean[par ^ 1] = true;
     if (marks && marks->rows_hashed) RBC_HIP(hipEventRecord((hipEvent_t)marks->rows_hashed, st));
-    if (hv && v_path) {
-        PathArgs p{};
-        p.count = cur->count;
-        p.n = c->n;
-        p.width = c->width;
-        p.lg_width = c->depth;
-        p.depth = c->depth;
-        p.leaves = cur->leaves;
-        p.leaves_inst_pitch = (uint64_t)c->n * 32;
-        p.branches = cur->branches;
-        p.br_inst_pitch = (uint64_t)c->n * c->depth * 32;
-        p.roots = cur->roots;
-        p.present = cur->present;
-        p.valid = cur->valid;
-        p.prio = c->rx_prio;
-        RBC_HIP(rbc_launch_merkle_path(p, st));
-    }
+    if ((rc = ev.finish(c, st))) return rc;  // the shared-path verify where the branch walk is a real share (C4)
     if (marks && marks->hashed) RBC_HIP(hipEventRecord((hipEvent_t)marks->hashed, st));
     // From here on prev's aux-stream work (its join from the previous call and
     // its digest) is joined back into `st` on every exit, errors included.
-    struct PrevJoin {
-        Ws &w;
-        hipStream_t st;
-        bool armed = false;
-        ~PrevJoin() {
-            if (armed) (void)hipStreamWaitEvent(st, w.ev_join, 0);
-        }
-    } pj{w, st};
+    JoinBack pj{w, st, false, false};  // ev_join is recorded below, before prev's recheck
     if (hp) {
         if (prev->digests) {  // beside the recheck, on the aux stream (after prev's join)
             RBC_HIP(hipEventRecord(w.ev_hashed, st));
@@ -933,17 +892,7 @@ int stage_receive_step(rbc_ctx *c, hipStream_t st, const rbc_rx_batch *cur, cons
         }
         RBC_HIP(hipEventRecord(w.ev_join, w.aux));  // prev's join (+ digest) done
         pj.armed = true;
-        MerkleArgs m{};
-        m.count = prev->count;
-        m.n = c->n;
-        m.width = c->width;
-        m.depth = c->depth;
-        m.k = c->k;
-        m.leaves = prev->leaves;
-        m.leaves_inst_pitch = (uint64_t)c->n * 32;
-        m.expect_roots = prev->roots;
-        m.status = prev->status;
-        m.prio = c->rx_prio;
+        MerkleArgs m = merkle_check_args(c, prev->count, prev->leaves, prev->roots, prev->status);
         if (reuse && w.rx_vreuse) {
             // the nodes inside the valid-free subtrees only; an instance whose
             // decode changed a valid row goes on to the full recheck (m.only)
@@ -981,16 +930,14 @@ int stage_receive_step(rbc_ctx *c, hipStream_t st, const rbc_rx_batch *cur, cons
     if (hc) {
         if (marks && marks->decode_begin) RBC_HIP(hipEventRecord((hipEvent_t)marks->decode_begin, st));
         bool joined = false;
-        rc = stage_regenerate(c, w, st, cur->count, cur->shards, cur->shard_pitch, cur->shard_lens,
-                              cur->uniform_shard_len, cur->valid, cur->status, 1, r_cnt, cur->values_out,
+        rc = stage_regenerate(c, w, st, cur->count, rx_rows(cur), cur->valid, cur->status, 1, r_cnt, cur->values_out,
                               cur->value_pitch, &joined);
         if (rc) return rc;
         if (marks && marks->decoded) RBC_HIP(hipEventRecord((hipEvent_t)marks->decoded, st));
         if (cur->values_out && !joined) {  // the row view (values_out NULL) has no join; the FFT decode joins
             RBC_HIP(hipEventRecord(w.ev_fork, st));
             RBC_HIP(hipStreamWaitEvent(w.aux, w.ev_fork, 0));
-            rc = launch_join(c, w.aux, cur->count, cur->shards, cur->shard_pitch, cur->shard_lens,
-                             cur->uniform_shard_len, cur->values_out, cur->value_pitch, cur->status);
+            rc = launch_join(c, w.aux, cur->count, rx_rows(cur), cur->values_out, cur->value_pitch, cur->status);
             if (rc) return rc;
         }
         w.rx_count = cur->count;
@@ -1047,7 +994,7 @@ int host_reconstruct(rbc_ctx *c, uint8_t *const *shards, size_t *lens, int n_sha
     if (!st) return RBC_ERR_DEVICE;
     RBC_HIP(hipMemcpyAsync(c->d_shards.p, stage, (size_t)c->n * pitch, hipMemcpyHostToDevice, st));
     RBC_HIP(hipMemcpyAsync(c->d_valid.p, stage + (size_t)c->n * pitch, c->n, hipMemcpyHostToDevice, st));
-    rc = stage_regenerate(c, c->ws, st, 1, c->d_shards.as<uint8_t>(), (uint32_t)pitch, nullptr, (uint32_t)S,
+    rc = stage_regenerate(c, c->ws, st, 1, {c->d_shards.as<uint8_t>(), (uint32_t)pitch, nullptr, (uint32_t)S},
                           c->d_valid.as<uint8_t>(), c->d_status.as<int32_t>());
     if (rc) return rc;
     RBC_HIP(hipMemcpyAsync(stage, c->d_shards.p, (size_t)c->n * pitch, hipMemcpyDeviceToHost, st));
@@ -1301,8 +1248,8 @@ int rbc_dev_leaves(rbc_ctx *c, void *stream, int count, const uint8_t *shards, u
                    const uint32_t *shard_lens, uint32_t uniform_shard_len, uint8_t *leaves) {
     if (!c) return RBC_ERR_INVALID_ARG;
     RBC_HIP(hipSetDevice(c->device));
-    return stage_leaves(c, as_stream(stream), count, {const_cast<uint8_t *>(shards), shard_pitch}, shard_lens,
-                        uniform_shard_len, leaves);
+    return stage_leaves(c, as_stream(stream), count,
+                        {const_cast<uint8_t *>(shards), shard_pitch, shard_lens, uniform_shard_len}, leaves);
 }
 
 int rbc_dev_merkle_build(rbc_ctx *c, void *stream, int count, const uint8_t *leaves, uint8_t *roots,
@@ -1332,7 +1279,7 @@ int rbc_dev_shard_commit_parity(rbc_ctx *c, void *stream, int count, const uint8
     if (count > 0 && (!leaves || !roots)) return RBC_ERR_INVALID_ARG;  // before the first launch
     RBC_HIP(hipSetDevice(c->device));
     return commit_stages(c, as_stream(stream), count, values, value_pitch, value_lens, uniform_value_len,
-                         {data_rows, row_pitch, true, parity}, shard_lens, leaves, roots, branches);
+                         {data_rows, row_pitch, nullptr, 0, true, parity}, shard_lens, leaves, roots, branches);
 }
 
 int rbc_dev_verify(rbc_ctx *c, void *stream, int count, const uint8_t *shards, uint32_t shard_pitch,
@@ -1340,8 +1287,9 @@ int rbc_dev_verify(rbc_ctx *c, void *stream, int count, const uint8_t *shards, u
                    const uint8_t *roots, const uint8_t *present, uint8_t *valid, uint8_t *leaves) {
     if (!c) return RBC_ERR_INVALID_ARG;
     RBC_HIP(hipSetDevice(c->device));
-    return stage_verify(c, as_stream(stream), count, shards, shard_pitch, shard_lens, uniform_shard_len, branches,
-                        roots, present, valid, leaves);
+    return stage_verify(c, as_stream(stream), count,
+                        {const_cast<uint8_t *>(shards), shard_pitch, shard_lens, uniform_shard_len}, branches, roots,
+                        present, valid, leaves);
 }
 
 int rbc_dev_interpolate(rbc_ctx *c, void *stream, int count, uint8_t *shards, uint32_t shard_pitch,
@@ -1353,7 +1301,7 @@ int rbc_dev_interpolate(rbc_ctx *c, void *stream, int count, uint8_t *shards, ui
     // the workspace holds a receive-step batch's regen list until its next call
     if (c->ws.rx_count > 0) return RBC_ERR_INVALID_ARG;
     RBC_HIP(hipSetDevice(c->device));
-    return stage_interpolate(c, c->ws, as_stream(stream), count, shards, shard_pitch, shard_lens, uniform_shard_len,
+    return stage_interpolate(c, c->ws, as_stream(stream), count, {shards, shard_pitch, shard_lens, uniform_shard_len},
                              valid, leaves, leaves_verified, roots, values_out, value_pitch, digests, status);
 }
 
@@ -1964,22 +1912,10 @@ int rbc_validate_batch(rbc_ctx *c, int count, const uint8_t *const *shards, cons
     RBC_HIP(hipMemcpyAsync(s.d_roots.p, rt, (size_t)count * 32, hipMemcpyHostToDevice, st));
     RBC_HIP(hipMemcpyAsync(s.d_slens.p, ln, (size_t)count * 4, hipMemcpyHostToDevice, st));
     RBC_HIP(hipMemcpyAsync(s.d_idx.p, ix, (size_t)count, hipMemcpyHostToDevice, st));
-    ShaArgs a{};
-    a.count = count;
-    a.rows_per_inst = 1;
-    a.rows = s.d_shards.as<uint8_t>();
-    a.inst_pitch = pitch;
-    a.row_pitch = 0;
-    a.lens = s.d_slens.as<uint32_t>();
-    a.idx = s.d_idx.as<uint8_t>();
-    a.idx_stride = 1;
-    a.per_message = 1;
-    a.n = c->n;
-    a.depth = d;
-    a.branches = s.d_branches.as<uint8_t>();
-    a.br_inst_pitch = bslot;
-    a.roots = s.d_roots.as<uint8_t>();
-    a.valid = s.d_valid.as<uint8_t>();
+    // (no prio: this launch runs at wave priority 0, whatever the context's receive-side level)
+    const ShaArgs a = sha_message_args(count, c->n, d, s.d_shards.as<uint8_t>(), pitch, s.d_slens.as<uint32_t>(),
+                                       s.d_idx.as<uint8_t>(), s.d_branches.as<uint8_t>(), bslot,
+                                       s.d_roots.as<uint8_t>(), s.d_valid.as<uint8_t>());
     RBC_HIP(rbc_launch_sha_rows(a, true, st));
     uint8_t *o_ok = s.h_out.as<uint8_t>();
     RBC_HIP(hipMemcpyAsync(o_ok, s.d_valid.p, (size_t)count, hipMemcpyDeviceToHost, st));
@@ -2074,26 +2010,12 @@ static int validate_packed(rbc_ctx *c, int count, const uint8_t *arena, size_t a
     RBC_HIP(hipMemcpyAsync(s.d_idx.p, idx, (size_t)count, hipMemcpyHostToDevice, st));
     RBC_HIP(hipMemcpyAsync(s.d_branches.p, branches, (size_t)count * bslot, hipMemcpyHostToDevice, st));
     RBC_HIP(hipMemcpyAsync(s.d_roots.p, roots, (size_t)count * 32, hipMemcpyHostToDevice, st));
-    ShaArgs a{};
-    a.count = count;
-    a.rows_per_inst = 1;
-    a.rows = d_arena;
+    // leaves_out: the message's SHA-256 leaf, [count][32] (interpolate_batch_verified reuses it)
+    ShaArgs a = sha_message_args(count, c->n, d, d_arena, 0, s.d_slens.as<uint32_t>(), s.d_idx.as<uint8_t>(),
+                                 s.d_branches.as<uint8_t>(), bslot, s.d_roots.as<uint8_t>(), s.d_valid.as<uint8_t>(),
+                                 leaves_out ? s.d_leaves.as<uint8_t>() : nullptr);
     a.row_offs = s.d_offs.as<uint64_t>();
-    a.lens = s.d_slens.as<uint32_t>();
-    a.idx = s.d_idx.as<uint8_t>();
-    a.idx_stride = 1;
-    a.per_message = 1;
-    a.n = c->n;
-    a.depth = d;
-    a.branches = s.d_branches.as<uint8_t>();
-    a.br_inst_pitch = bslot;
-    a.roots = s.d_roots.as<uint8_t>();
-    a.valid = s.d_valid.as<uint8_t>();
     a.prio = c->rx_prio;
-    if (leaves_out) {  // the message's SHA-256 leaf, [count][32] (interpolate_batch_verified reuses it)
-        a.leaves = s.d_leaves.as<uint8_t>();
-        a.leaves_inst_pitch = 32;
-    }
     RBC_HIP(rbc_launch_sha_rows(a, true, st));
     void *d_valid = s.d_valid.p, *d_lv = s.d_leaves.p;
     auto d2h = [=](hipStream_t cs) -> int {  // behind the next submission's H2D (Slot::d2h)
@@ -2273,20 +2195,18 @@ static int host_receive(rbc_ctx *c, int count, const uint8_t *shards, size_t sha
     if (leaves)  // 32 B per row (1/744 of a C2 row): the whole [count][n][32] block in one copy
         RBC_HIP(hipMemcpyAsync(s.d_leaves.p, leaves, (size_t)count * n * 32, hipMemcpyHostToDevice, st));
     int rc = RBC_OK;
+    const Rows d_rows{s.d_shards.as<uint8_t>(), (uint32_t)dpitch, s.d_slens.as<uint32_t>()};
     if (branches) {  // validateMessage of every present row on the device, its leaves kept for interpolate
         RBC_HIP(hipMemcpyAsync(s.d_branches.p, branches, br_bytes, hipMemcpyHostToDevice, st));
-        rc = stage_verify(c, st, count, s.d_shards.as<uint8_t>(), (uint32_t)dpitch, s.d_slens.as<uint32_t>(), 0,
-                          s.d_branches.as<uint8_t>(), s.d_roots.as<uint8_t>(), d_pres, s.d_valid.as<uint8_t>(),
-                          s.d_leaves.as<uint8_t>(), &s.ws);
+        rc = stage_verify(c, st, count, d_rows, s.d_branches.as<uint8_t>(), s.d_roots.as<uint8_t>(), d_pres,
+                          s.d_valid.as<uint8_t>(), s.d_leaves.as<uint8_t>(), &s.ws);
         if (rc) return rc;
     }
     // ragged batch: bytes past k*S_i of a value row are returned as zero
     RBC_HIP(hipMemsetAsync(s.d_values.p, 0, (size_t)count * vpitch, st));
-    rc = stage_interpolate(c, s.ws, st, count, s.d_shards.as<uint8_t>(), (uint32_t)dpitch,
-                               s.d_slens.as<uint32_t>(), 0, s.d_valid.as<uint8_t>(), s.d_leaves.as<uint8_t>(),
-                               (leaves || branches) ? 1 : 0,
-                               s.d_roots.as<uint8_t>(), s.d_values.as<uint8_t>(), (uint32_t)vpitch,
-                               s.d_digests.as<uint8_t>(), s.d_status.as<int32_t>());
+    rc = stage_interpolate(c, s.ws, st, count, d_rows, s.d_valid.as<uint8_t>(), s.d_leaves.as<uint8_t>(),
+                           (leaves || branches) ? 1 : 0, s.d_roots.as<uint8_t>(), s.d_values.as<uint8_t>(),
+                           (uint32_t)vpitch, s.d_digests.as<uint8_t>(), s.d_status.as<int32_t>());
     if (rc) return rc;
     uint8_t *o_val = s.h_out.as<uint8_t>(), *o_dig = o_val + out_stage;
     int32_t *o_st = reinterpret_cast<int32_t *>(o_dig + (size_t)count * 32);
@@ -2497,7 +2417,7 @@ int rbc_interpolate(rbc_ctx *c, const uint8_t *root, const uint8_t *const *shard
     RBC_HIP(hipMemcpyAsync(s.d_shards.p, i_sh, sh_bytes, hipMemcpyHostToDevice, st));
     RBC_HIP(hipMemcpyAsync(s.d_valid.p, i_pr, npad + 32, hipMemcpyHostToDevice, st));  // present + root
     const uint8_t *d_root = s.d_valid.as<uint8_t>() + npad;
-    rc = stage_interpolate(c, s.ws, st, 1, s.d_shards.as<uint8_t>(), (uint32_t)dpitch, nullptr, (uint32_t)S,
+    rc = stage_interpolate(c, s.ws, st, 1, {s.d_shards.as<uint8_t>(), (uint32_t)dpitch, nullptr, (uint32_t)S},
                            s.d_valid.as<uint8_t>(), s.d_leaves.as<uint8_t>(), 0, d_root, s.d_values.as<uint8_t>(),
                            (uint32_t)vpitch, s.d_digests.as<uint8_t>(), s.d_status.as<int32_t>());
     if (rc) return rc;

@@ -81,6 +81,35 @@ struct ShaArgs {
     int prio;                  // wave issue priority 0..3 (set_wave_prio)
 };
 
+// validateMessage per message (sha_rows_kernel<true>, per_message): instance i
+// is one ECHO of lens[i] bytes at rows + i * msg_pitch (a caller with packed
+// messages sets row_offs instead) from leaf idx[i], its branch at branches +
+// i * bslot and its root at roots + 32 i; valid[i] = the verdict, leaves
+// (nullable) [count][32] = the message's leaf.  The caller adds what only it
+// has: row_offs, row_pitch, status, prio.
+inline ShaArgs sha_message_args(int count, int n, int depth, const uint8_t *rows, uint64_t msg_pitch,
+                                const uint32_t *lens, const uint8_t *idx, const uint8_t *branches, uint64_t bslot,
+                                const uint8_t *roots, uint8_t *valid, uint8_t *leaves = nullptr) {
+    ShaArgs a{};
+    a.count = count;
+    a.rows_per_inst = 1;
+    a.rows = rows;
+    a.inst_pitch = msg_pitch;
+    a.lens = lens;
+    a.idx = idx;
+    a.idx_stride = 1;
+    a.leaves = leaves;
+    a.leaves_inst_pitch = leaves ? 32 : 0;
+    a.per_message = 1;
+    a.n = n;
+    a.depth = depth;
+    a.branches = branches;
+    a.br_inst_pitch = bslot;
+    a.roots = roots;
+    a.valid = valid;
+    return a;
+}
+
 struct MerkleArgs {
     int count, n, width, depth, k;
     const uint8_t *leaves;     // [I][N][32]

@@ -188,25 +188,10 @@ int rbc_wire_validate(rbc_wire_rx *rx, int count, const uint8_t *ring, size_t ri
     u.codec = codec;
     WIRE_HIP(rbc_launch_unmarshal_val(u, st));
     // validateMessage per decoded message (fallback messages are skipped by their status)
-    ShaArgs a{};
-    a.count = count;
-    a.rows_per_inst = 1;
-    a.rows = keep_dev;
-    a.inst_pitch = rx->row_pitch;
+    ShaArgs a = sha_message_args(count, rx->n, rx->depth, keep_dev, rx->row_pitch, u.shard_lens, u.idx,
+                                 rx->d_branches, rx->bslot, u.roots, rx->d_small + so.valid, rx->d_small + so.leaves);
     a.row_pitch = rx->row_pitch;
-    a.lens = u.shard_lens;
-    a.idx = u.idx;
-    a.idx_stride = 1;
     a.status = u.status;
-    a.per_message = 1;
-    a.n = rx->n;
-    a.depth = rx->depth;
-    a.branches = rx->d_branches;
-    a.br_inst_pitch = rx->bslot;
-    a.roots = u.roots;
-    a.valid = rx->d_small + so.valid;
-    a.leaves = rx->d_small + so.leaves;
-    a.leaves_inst_pitch = 32;
     WIRE_HIP(rbc_launch_sha_rows(a, true, st));
     WIRE_HIP(hipMemcpyAsync(rx->h_small, rx->d_small, so.bytes, hipMemcpyDeviceToHost, st));
     WIRE_HIP(hipEventRecord(rx->done, st));

@@ -194,10 +194,16 @@ static void fuzz_interpolate_batch(Geo &g) {
     const bool async = coin(50);
     // ABI 6: half the calls hand in the present rows' leaves [count][n][32]
     std::vector<uint8_t> leaves = bytes((size_t)count * g.n * 32 + 1);
-    const int rc = rbc_interpolate_batch_verified(g.ctx, count, shards.data(), pitch, sl.data(), present.data(),
-                                                  coin(50) ? leaves.data() : nullptr, roots.data(), values.data(),
-                                                  vpitch, coin(30) ? nullptr : digests.data(), status.data(),
-                                                  async ? &t : nullptr);
+    // or the ECHO verify on the device first: branches in, verdicts [count][n] out
+    std::vector<uint8_t> br = bytes((size_t)count * g.n * std::max(g.d, 1) * 32 + 1), valid((size_t)count * g.n + 1);
+    const int rc = coin(40) ? rbc_receive_batch(g.ctx, count, shards.data(), pitch, sl.data(), present.data(), br.data(),
+                                                roots.data(), valid.data(), values.data(), vpitch,
+                                                coin(30) ? nullptr : digests.data(), status.data(), async ? &t : nullptr)
+                            : rbc_interpolate_batch_verified(g.ctx, count, shards.data(), pitch, sl.data(),
+                                                             present.data(), coin(50) ? leaves.data() : nullptr,
+                                                             roots.data(), values.data(), vpitch,
+                                                             coin(30) ? nullptr : digests.data(), status.data(),
+                                                             async ? &t : nullptr);
     bool bad = vpitch < (size_t)g.k * Smax;
     for (int i = 0; i < count; ++i) bad |= sl[i] > pitch;
     if (count > 0 && bad) EXPECT(rc == RBC_ERR_INVALID_ARG);
@@ -425,12 +431,30 @@ static void fuzz_acs() {
 
 // Device API: argument checks with buffers sized per the contract for the
 // (bounded) random scalars; the stub kernels touch what the real ones write.
+// The receive step, rbc_dev_verify and rbc_dev_interpolate over every form of
+// their launches: both codecs and both recheck modes, ragged and uniform
+// lengths, rows long enough for the per-leaf walk and for the decode's fused
+// join (uniform S >= 2048, a value tail of at most 256 B) and value pitches
+// too long for it, batches verified beforehand, timing marks.
 static void fuzz_receive_step(Geo &g) {
-    const int count = 1 + (int)rnd(4);
-    const uint32_t pitch = 64 * (1 + (uint32_t)rnd(8));
-    const uint32_t S = coin(85) ? 1 + (uint32_t)rnd(pitch) : pitch + 64;
-    const bool view = coin(50);
-    const uint32_t vpitch = view ? 0 : 16 * ((g.k * S + 15) / 16 + (uint32_t)rnd(3));
+    const bool big = coin(15);  // rows of 2112 .. 4160 B
+    const int count = 1 + (int)rnd(big ? 2 : 4);
+    const uint32_t pitch = 64 * (big ? 33 + (uint32_t)rnd(33) : 1 + (uint32_t)rnd(8));
+    const uint32_t S = coin(85) ? (big ? 2048 : 1) + (uint32_t)rnd(pitch - (big ? 2047 : 0)) : pitch + 64;
+    const bool view = coin(50), ragged = coin(25);
+    const uint32_t Smax = ragged ? pitch : S;  // ragged: every S_i <= pitch, the uniform length is ignored
+    // a value row: k*Smax bytes, a short pad, now and then more than the fused join zero-fills
+    const uint32_t vpitch = view ? 0 : 16 * ((g.k * Smax + 15) / 16 + (uint32_t)rnd(3) + (coin(20) ? 20 : 0));
+    rbc_ctx *ctx = g.ctx;
+    EXPECT(rbc_ctx_set_codec(ctx, coin(35) ? RBC_CODEC_MATRIX : RBC_CODEC_AUTO) == RBC_OK);
+    EXPECT(rbc_ctx_set_recheck(ctx, coin(50) ? RBC_RECHECK_FULL : RBC_RECHECK_REUSE) == RBC_OK);
+    rbc_rx_marks marks{};
+    void **mark[] = {&marks.hashed,     &marks.decode_begin, &marks.decoded,
+                     &marks.hash_begin, &marks.rows_hashed,  &marks.prev_released};
+    const bool with_marks = coin(40);
+    for (void **m : mark)
+        if (with_marks && coin(70)) EXPECT(rbc_event_create(m) == RBC_OK);
+    const rbc_rx_marks *mk_arg = with_marks ? &marks : nullptr;
     auto dev = [](size_t b) {
         void *p = nullptr;
         rbc_dev_malloc(0, b, &p);
@@ -448,6 +472,14 @@ static void fuzz_receive_step(Geo &g) {
         b.shards = mk((size_t)count * g.n * pitch);
         b.shard_pitch = pitch;
         b.uniform_shard_len = S;
+        if (ragged) {
+            std::vector<uint32_t> sl(count);
+            for (auto &s : sl) s = 1 + (uint32_t)rnd(pitch);
+            uint8_t *d = mk((size_t)count * 4);
+            EXPECT(rbc_memcpy_h2d(d, sl.data(), (size_t)count * 4) == RBC_OK);
+            b.shard_lens = (const uint32_t *)d;
+        }
+        b.verified = coin(25);
         b.branches = mk((size_t)count * g.n * std::max(g.d, 1) * 32);
         b.roots = mk((size_t)count * 32);
         b.present = coin(70) ? mk((size_t)count * g.n) : nullptr;
@@ -462,17 +494,25 @@ static void fuzz_receive_step(Geo &g) {
     rbc_rx_batch a = batch(), b = batch();
     const bool alias = coin(20);
     if (alias) b.leaves = a.leaves;
-    const bool bad = S > pitch;
-    EXPECT(rbc_dev_receive_step(g.ctx, nullptr, &a, nullptr, nullptr) == (bad ? RBC_ERR_INVALID_ARG : RBC_OK));
+    const bool bad = !ragged && S > pitch;
+    // ECHO verify alone, with and without the present mask and the leaves
+    EXPECT(rbc_dev_verify(ctx, nullptr, count, a.shards, pitch, a.shard_lens, S, a.branches, a.roots,
+                          coin(50) ? a.present : nullptr, a.valid, coin(50) ? a.leaves : nullptr) ==
+           (bad ? RBC_ERR_INVALID_ARG : RBC_OK));
+    EXPECT(rbc_dev_receive_step(ctx, nullptr, &a, nullptr, mk_arg) == (bad ? RBC_ERR_INVALID_ARG : RBC_OK));
     if (!bad) {
-        EXPECT(rbc_dev_interpolate(g.ctx, nullptr, count, a.shards, pitch, nullptr, S, a.valid, a.leaves, 1, a.roots,
+        EXPECT(rbc_dev_interpolate(ctx, nullptr, count, a.shards, pitch, a.shard_lens, S, a.valid, a.leaves, 1, a.roots,
                                    nullptr, 0, nullptr, a.status) == RBC_ERR_INVALID_ARG);  // a batch is pending
-        EXPECT(rbc_dev_receive_step(g.ctx, nullptr, &b, &a, nullptr) == (alias ? RBC_ERR_INVALID_ARG : RBC_OK));
-        EXPECT(rbc_dev_receive_step(g.ctx, nullptr, nullptr, alias ? &a : &b, nullptr) == RBC_OK);
+        EXPECT(rbc_dev_receive_step(ctx, nullptr, &b, &a, mk_arg) == (alias ? RBC_ERR_INVALID_ARG : RBC_OK));
+        EXPECT(rbc_dev_receive_step(ctx, nullptr, nullptr, alias ? &a : &b, mk_arg) == RBC_OK);
     }
-    EXPECT(rbc_dev_interpolate(g.ctx, nullptr, count, a.shards, pitch, nullptr, S, a.valid, a.leaves, 1, a.roots,
+    EXPECT(rbc_dev_interpolate(ctx, nullptr, count, a.shards, pitch, a.shard_lens, S, a.valid, a.leaves, coin(70), a.roots,
                                a.values_out, vpitch, a.digests, a.status) == (bad ? RBC_ERR_INVALID_ARG : RBC_OK));
     for (void *p : owned) rbc_dev_free(p);
+    for (void **m : mark)
+        if (*m) rbc_event_destroy(*m);
+    EXPECT(rbc_ctx_set_codec(ctx, RBC_CODEC_AUTO) == RBC_OK);  // the other drivers run the context's own codec
+    EXPECT(rbc_ctx_set_recheck(ctx, RBC_RECHECK_REUSE) == RBC_OK);
 }
 
 int main(int argc, char **argv) {
