@@ -217,28 +217,28 @@ hipError_t rbc_launch_gf_regen(const GfArgs &a, hipStream_t st) {
     if (a.count <= 0 || a.R <= 0) return hipSuccess;
     if (a.mode != GF_MODE_DECODE || !a.rcount || a.nmiss || a.copy || a.K < 1 || a.K > 248 || a.out_row_pitch % 4u)
         return hipErrorInvalidValue;
-    // one wave per column tile owns every missing row: 512-B tiles (8 B per
-    // lane), or 256 B (4 B per lane) for rows of at most 2 KiB, where they keep
-    // the lanes busy (C4: S = 763 -> 3 tiles, 99 %)
-    const uint32_t S = a.lens ? a.out_row_pitch : a.uniform_len;
+    // one wave per column tile owns every missing row; the tile width, the rows
+    // per pass and the tiles per block are host_shared.h's rbc_gf_regen_form
     // (C4's 768-B row as ONE tile of 12 B per lane, a wave owning the whole
     // instance at 167 VGPRs: 308-312 against 320 GB/s, tools/gpu_runs/gpu_r04e.sh)
-    const int W = S <= 2048 ? 1 : 2;
+    const RbcRegenForm form = rbc_gf_regen_form(a.lens != nullptr, a.uniform_len, a.out_row_pitch);
+    const int W = form.W;
     GfArgs b = a;
     b.wpt = W;
     b.tiles = (int)((a.out_row_pitch + 256u * W - 1) / (256u * W));
     constexpr int JC = 16;  // inputs per table chunk; 8 measured the same at C2 and C4 (gpu_r04i.sh)
     const int KP = (a.K + 3) & ~3;
-    auto go = [&](auto kern, int RC, int NT) {
+    auto go = [&](auto kern) {
+        const int RC = form.RC, NT = form.NT;
         const uint64_t blocks = (uint64_t)b.count * ((b.tiles + NT - 1) / NT);
         if (blocks > 0x7fffffffull) return hipErrorInvalidValue;
         const size_t lds = 2 * (size_t)24 * RC * JC + 4 * (size_t)(KP + 8);
         hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(64 * NT), lds, st, b);
         return hipGetLastError();
     };
-    if (W == 1)  // short rows (C4: S = 763, 3 tiles of 256 B; m ~ 29 +- 4 of k = 86 in one pass)
-        return go(gf_regen_kernel<1, 40, JC, 3, 4>, 40, 3);
-    // long rows (C1-C3: m ~ 7-15 of k = 22-44): 512-B tiles, four to a block
-    return go(gf_regen_kernel<2, 24, JC, 4, 4>, 24, 4);
+    if (W == 1)  // short rows: 256-B tiles, three to a block
+        return go(gf_regen_kernel<1, kRegenRowsShort, JC, kRegenTilesShort, 4>);
+    // long rows: 512-B tiles, four to a block
+    return go(gf_regen_kernel<2, kRegenRowsLong, JC, kRegenTilesLong, 4>);
 }
 

@@ -55,6 +55,23 @@ inline int rbc_gf_pick_rc_impl(int R, int rcmax) {
     return 48;
 }
 
+// The form of gf_regen_kernel (gf_regen.hip) that rbc_launch_gf_regen runs: one
+// wave per column tile of 64 lanes x W words owns every missing row, in passes
+// of at most RC rows (one straight-line body per exact row count 1..RC), NT
+// tiles to a block.  512-B tiles (W = 2), or 256-B tiles (W = 1) for rows of at
+// most 2 KiB, where they keep the lanes busy (C4: S = 763 -> 3 tiles, 99 %).
+// The row length is the uniform one, or the pitch when lengths are per instance.
+constexpr int kRegenRowsShort = 40, kRegenTilesShort = 3;  // W = 1 (C4: m ~ 29 +- 4 of k = 86 in one pass)
+constexpr int kRegenRowsLong = 24, kRegenTilesLong = 4;    // W = 2 (C1-C3: m ~ 7-15 of k = 22-44)
+struct RbcRegenForm {
+    int W, RC, NT;
+};
+inline RbcRegenForm rbc_gf_regen_form(bool per_instance_lens, uint32_t uniform_len, uint32_t row_pitch) {
+    const uint32_t S = per_instance_lens ? row_pitch : uniform_len;
+    if (S <= 2048) return {1, kRegenRowsShort, kRegenTilesShort};
+    return {2, kRegenRowsLong, kRegenTilesLong};
+}
+
 // klauspost Split's data shards without copying whole rows (rbc/rbc.go:97-100:
 // Split returns slices of the caller's value, and allocates only where it has
 // to pad).  With S = ceil(len / k), row j is data[j*S, (j+1)*S) itself while it

@@ -459,8 +459,8 @@ __global__ __launch_bounds__(256) void unmarshal_val_kernel(WireRxArgs a) {
 // knows which instance a message belongs to and which root that instance
 // collects ECHOs for.  The shard and the branch go straight to slot
 // r = inst*n + idx of the rbc_rx_batch layout (what sha_rows / the decode
-// read), so a shard is written once; the message's root is only compared, in
-// registers, with roots[inst].  Same shape derivation, same byte checks, same
+// read), so a shard is written once, and only once its message is accepted;
+// the message's root is only compared, in registers, with roots[inst].  Same shape derivation, same byte checks, same
 // chunk decode; the status order is kernels.h's (WireEchoArgs).
 // one wave per message; 4 waves (messages) per block
 __global__ __launch_bounds__(256) void unmarshal_echo_kernel(WireEchoArgs a) {
@@ -504,34 +504,50 @@ __global__ __launch_bounds__(256) void unmarshal_echo_kernel(WireEchoArgs a) {
     uint8_t *row = a.shards + r * a.shard_pitch;
     uint8_t *slot = branch_slot(a.branches, r, a.depth);
     const uint8_t *want_root = a.roots + (size_t)in * 32;
-    for (uint32_t q = lane; q < nq; q += 64) {
-        uint32_t off, len, o0;
-        uint8_t *dst;
+    // chunk q: its run, its place in the run and where it goes (NULL: the root)
+    auto chunk = [&](uint32_t q, uint32_t &off, uint32_t &len, uint32_t &o0) -> uint8_t * {
         if (q < nblk) {
             off = L.blk_off, len = S, o0 = q << 4;
-            dst = row;
-        } else if (q < nblk + nbr) {
+            return row;
+        }
+        if (q < nblk + nbr) {
             off = L.br_off, len = br_len, o0 = (q - nblk) << 4;
-            dst = slot + (empty0 ? 32u : 0u);
-        } else {
-            off = L.root_off, len = 32, o0 = (q - nblk - nbr) << 4;
-            dst = nullptr;
+            return slot + (empty0 ? 32u : 0u);
         }
+        off = L.root_off, len = 32, o0 = (q - nblk - nbr) << 4;
+        return nullptr;
+    };
+    // A rejected message leaves its slot as it was, so every character is
+    // checked and the root compared before the first store.  The lane's first
+    // chunk stays in registers (all of a message of up to 64 chunks, ~1 KB);
+    // the chunks behind it are decoded a second time for the store.
+    uint4 first = make_uint4(0, 0, 0, 0);
+    for (uint32_t q = lane; q < nq; q += 64) {
+        uint32_t off, len, o0;
+        const uint8_t *dst = chunk(q, off, len, o0);
         const uint4 v = unb64_chunk(m, off, len, o0, bad);
-        if (dst) {
-            *reinterpret_cast<uint4 *>(dst + o0) = v;
-        } else {
-            const uint4 w = *reinterpret_cast<const uint4 *>(want_root + o0);
-            other |= (v.x ^ w.x) | (v.y ^ w.y) | (v.z ^ w.z) | (v.w ^ w.w);
+        if (q == lane) first = v;
+        if (!dst) other |= root_diff(v, want_root + o0);
+    }
+    const bool fail = __any(bad != 0), wrong = __any(other != 0);
+    if (fail || wrong) {
+        if (lane == 0) {
+            a.msg_status[i] = fail ? WIRE_FALLBACK : WIRE_OTHER_ROOT;
+            if (a.types) a.types[i] = (uint8_t)type;
         }
+        return;
+    }
+    for (uint32_t q = lane; q < nq; q += 64) {
+        uint32_t off, len, o0, again = 0;
+        uint8_t *dst = chunk(q, off, len, o0);
+        if (dst) *reinterpret_cast<uint4 *>(dst + o0) = q == lane ? first : unb64_chunk(m, off, len, o0, again);
     }
     // the zero slot of an empty level-0 sibling (or of a depth-0 tree)
     if ((empty0 || a.depth == 0) && lane < 2) reinterpret_cast<uint4 *>(slot)[lane] = make_uint4(0, 0, 0, 0);
-    const bool fail = __any(bad != 0), wrong = __any(other != 0);
     if (lane == 0) {
-        a.msg_status[i] = fail ? WIRE_FALLBACK : wrong ? WIRE_OTHER_ROOT : WIRE_OK;
+        a.msg_status[i] = WIRE_OK;
         if (a.types) a.types[i] = (uint8_t)type;
-        if (!fail && !wrong) a.present[r] = 1;
+        a.present[r] = 1;
     }
 }
 
@@ -922,32 +938,38 @@ __global__ __launch_bounds__(256) void unmarshal_echo_bin_kernel(WireEchoArgs a)
         }
         return;
     }
-    // shard and branch to slot r; the two chunks of the root are compared, not stored
+    // the two chunks of the root are compared, not stored, and before any
+    // store: a message for another root leaves its slot as it was
     const uint32_t rt = (total + 15u) & ~15u;
-    const uint32_t nblk = ((S + 63u) & ~63u) >> 4, nbr = 2 * L, nq = nblk + nbr + 2;
+    const uint32_t nblk = ((S + 63u) & ~63u) >> 4, nbr = 2 * L, nq = nblk + nbr;
     const size_t r = (size_t)in * a.n + j;
     uint8_t *row = a.shards + r * a.shard_pitch;
     uint8_t *slot = branch_slot(a.branches, r, a.depth);
     const uint8_t *want_root = a.roots + (size_t)in * 32;
     uint32_t other = 0;
+    if (lane < 2) other = root_diff(bin_chunk16(m, rt, c.root_off, 32, lane << 4), want_root + (lane << 4));
+    if (__any(other != 0)) {
+        if (lane == 0) {
+            a.msg_status[i] = WIRE_OTHER_ROOT;
+            if (a.types) a.types[i] = (uint8_t)type;
+        }
+        return;
+    }
+    // shard and branch to slot r
     for (uint32_t q = lane; q < nq; q += 64) {
         if (q < nblk) {
             *reinterpret_cast<uint4 *>(row + (q << 4)) = bin_chunk16(m, rt, c.blk_off, S, q << 4);
-        } else if (q < nblk + nbr) {
+        } else {
             const uint32_t o0 = (q - nblk) << 4;
             *reinterpret_cast<uint4 *>(slot + (empty0 ? 32u : 0u) + o0) = bin_chunk16(m, rt, c.br_off, 32 * L, o0);
-        } else {
-            const uint32_t o0 = (q - nblk - nbr) << 4;
-            other |= root_diff(bin_chunk16(m, rt, c.root_off, 32, o0), want_root + o0);
         }
     }
     // the zero slot of an empty level-0 sibling (or of a depth-0 tree)
     if ((empty0 || a.depth == 0) && lane < 2) reinterpret_cast<uint4 *>(slot)[lane] = make_uint4(0, 0, 0, 0);
-    const bool wrong = __any(other != 0);
     if (lane == 0) {
-        a.msg_status[i] = wrong ? WIRE_OTHER_ROOT : WIRE_OK;
+        a.msg_status[i] = WIRE_OK;
         if (a.types) a.types[i] = (uint8_t)type;
-        if (!wrong) a.present[r] = 1;
+        a.present[r] = 1;
     }
 }
 

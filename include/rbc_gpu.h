@@ -163,6 +163,8 @@ int rbc_device_mem_info(int device, size_t *free_bytes, size_t *total_bytes);
  * be zero).  After interpolate or the receive step every regenerated row (an
  * absent position, or an ECHO that did not verify) is zero there.  The pad of
  * a received row is unspecified after the call.
+ * The device stages are tested with 256-byte aligned buffers, as hipMalloc
+ * returns them.
  * `count` may exceed 65535 on either codec (the FFT launch carries the
  * instance in gridDim.y, which the runtime accepts; tested at 65547).       */
 

@@ -177,18 +177,17 @@ int rbc_wire_poll(rbc_wire_rx *rx, uint64_t ticket, int *done);
  * sibling) and present [count][n].  msg_status[m], decided in this order:
  *   1. the shape cannot be derived from lens[m] and idx[m] (rbc_dev_unmarshal_val's
  *      rule)                                          -> RBC_WIRE_FALLBACK
- *   2. the derived shard length is not the instance's -> RBC_WIRE_OTHER_LEN;
- *      nothing of the slot is written
+ *   2. the derived shard length is not the instance's -> RBC_WIRE_OTHER_LEN
  *   3. a byte is not canonical                        -> RBC_WIRE_FALLBACK
  *   4. the message's root (compared on the device, never stored) is not
  *      roots[inst[m]]                                 -> RBC_WIRE_OTHER_ROOT
  *   5. otherwise RBC_WIRE_OK: present[r] = 1, the row holds the shard with
  *      zeros from S to round_up(S, 64), the branch slot the device-form branch.
- * For statuses 1 and 2 present[r] is not written and the slot's row and branch
- * bytes are unspecified.  types[m] (types nullable) is the message's type for
- * RBC_WIRE_OK.  A message writes nothing outside its own row slot, branch
- * slot, present[r], msg_status[m] and types[m]; two messages naming one slot
- * are the caller's error.  All pointers are device memory, 16-byte aligned;
+ * A message with status 1, 2 or 3 writes nothing of its slot: row, branch slot
+ * and present[r] stay as they were.  types[m] (types nullable) is the
+ * message's type for RBC_WIRE_OK.  A message writes nothing outside its own row
+ * slot, branch slot, present[r], msg_status[m] and types[m]; two messages
+ * naming one slot are the caller's error.  All pointers are device memory, 16-byte aligned;
  * shard_pitch % 64 == 0 and >= every shard_lens[i].  The caller zeroes present
  * before the call, and shards where its consumer needs whole-pitch zeros. */
 #define RBC_HAS_WIRE_RECEIVE 1

@@ -1,18 +1,22 @@
-"""Python mirrors of the two launch rules in cleisthenes_amd/csrc/host_shared.h,
+"""Python mirrors of the three launch rules in cleisthenes_amd/csrc/host_shared.h,
 and the shapes the GPU tests pick by them.
 
 * trees_per_block(width, count) == rbc_trees_per_block: the trees
   (merkle_kernel) or instances (merkle_recheck_kernel) packed into a one-wave
   block;
 * gf_pick_rc(R, rcmax) == rbc_gf_pick_rc_impl, the body of rbc_gf_pick_rc:
-  the gf_rows_kernel<RC> body that serves R output rows.
+  the gf_rows_kernel<RC> body that serves R output rows;
+* gf_regen_form(per_instance_lens, uniform_len, row_pitch) == rbc_gf_regen_form:
+  the (W, RC, NT) of the gf_regen_kernel that rbc_launch_gf_regen runs, whose
+  passes are one straight-line body per exact row count 1 .. RC.
 
 tests/test_launch_rules.py (no GPU) builds tests/cpp/launch_rules_check.cpp
 from the header and compares its output with these mirrors, and asserts that
-PACKED_CASES reach G = 2 .. 64 and GF_CONTEXT_F / GF_ENCODER_P reach every
-RC in 1 .. 21: a changed launcher rule fails there instead of quietly moving
-tests/test_gpu_packed_merkle.py and tests/test_gpu_gf_bodies.py onto other
-launch shapes."""
+PACKED_CASES reach G = 2 .. 64, GF_CONTEXT_F / GF_ENCODER_P reach every
+RC in 1 .. 21 and REGEN_BODY_CASES reach every (W, rows) pass body of
+gf_regen_kernel: a changed launcher rule fails there instead of quietly moving
+tests/test_gpu_packed_merkle.py, tests/test_gpu_gf_bodies.py and
+tests/test_gpu_regen_bodies.py onto other launch shapes."""
 
 GF_RC_MAX = 21  # kGfRcMax
 K_RC = [1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11, 12, 13, 14, 15, 16, 17, 18, 19, 20, 21, 22, 23, 24, 26, 28, 30, 32, 36,
@@ -76,3 +80,42 @@ GF_ENCODER_K = [1, 2, 7, 8]
 
 def context_rc(f):
     return gf_pick_rc(2 * f)
+
+
+# gf_regen_kernel: the interpolate of the FFT codec regenerates the m missing
+# data rows of an instance in passes of RC rows, then one of m % RC.
+REGEN_FORMS = {1: (1, 40, 3), 2: (2, 24, 4)}  # W -> (W, RC, NT)
+
+
+def gf_regen_form(per_instance_lens, uniform_len, row_pitch):
+    S = row_pitch if per_instance_lens else uniform_len
+    return REGEN_FORMS[1 if S <= 2048 else 2]
+
+
+def regen_pass_rows(m, rc):
+    """The row counts of the passes that regenerate m rows: the bodies run."""
+    return [min(rc, m - r0) for r0 in range(0, m, rc)]
+
+
+# (n, f, S, the missing data rows m_i of instance i): S = 260 at pitch 320 is
+# two 256-byte tiles for three waves, the second 64 bytes wide; S = 2049 at
+# pitch 2112 is five 512-byte tiles in groups of four.  (64,21) has K = 22,
+# KP = 24 (zero-coefficient padding), (16,5) K = 6 < JC, (256,85) K = 86, KP = 88.
+REGEN_S_SHORT, REGEN_S_LONG = 260, 2049
+REGEN_BODY_CASES = [
+    (256, 85, REGEN_S_SHORT, list(range(1, 41))),
+    (128, 42, REGEN_S_SHORT, list(range(1, 41))),
+    (64, 21, REGEN_S_SHORT, list(range(1, 23))),
+    (16, 5, REGEN_S_SHORT, list(range(1, 7))),
+    (4, 1, REGEN_S_SHORT, [1, 2]),
+    (128, 42, REGEN_S_LONG, list(range(1, 25))),
+    (256, 85, REGEN_S_LONG, list(range(1, 25))),
+    (64, 21, REGEN_S_LONG, list(range(1, 23))),
+    (16, 5, REGEN_S_LONG, list(range(1, 7))),
+]
+
+
+def regen_case_bodies(n, f, S, ms):
+    """The (W, rows) pass bodies one uniform-length batch of the case runs."""
+    W, rc, _ = gf_regen_form(False, S, (S + 63) // 64 * 64)
+    return {(W, rows) for m in ms for rows in regen_pass_rows(m, rc)}

@@ -2,8 +2,10 @@
 device API (rbc_dev_verify, rbc_dev_interpolate, rbc_dev_receive_step): one
 small batch of committed values, the ECHO rows a receiver holds, and what
 interpolate must leave in every buffer.  Used by test_gpu_decode_n128.py,
-test_gpu_receive_step_overlap.py, test_gpu_receiver_contract.py and (the
-references against each other, no device) test_rx_cases_host.py."""
+test_gpu_receive_step_overlap.py, test_gpu_receiver_contract.py,
+test_gpu_dev_arena.py and test_gpu_regen_bodies.py (through dev_arena.py: the
+same buffers as regions of one guarded allocation) and (the references against
+each other, no device) test_rx_cases_host.py."""
 import numpy as np
 
 import rbc_ref
@@ -11,6 +13,8 @@ import rbc_ref
 PATTERNS = ("none", "worst", "parity", "corrupt_data", "corrupt_parity", "byzantine")
 # non-codewords with data rows absent: which k valid rows are used decides the re-encoding
 GONE_PATTERNS = ("byzantine_data_gone", "kth_at")
+# honest codewords with a chosen number of data rows absent (test_gpu_regen_bodies.py)
+COUNT_PATTERNS = ("data_missing",)
 VALUE_FILL, DIGEST_FILL = 0xA5, 0x5A  # DevCase's prefill of values / digests
 
 
@@ -54,6 +58,8 @@ class Case:
                       at least one valid row lies above it: those are unused and
                       are replaced by the re-encoding.  `honest` names instances
                       that are pattern `worst` instead.
+      data_missing    instance i misses exactly missing[i] data rows, at random
+                      positions, and holds every parity row.
     byz / corrupt: instance indices that get the byzantine / corrupt_data
     treatment on top of `pattern` (the receive-step test mixes them).
     lens: per-instance shard lengths (S and count may then be None): the pitch
@@ -65,8 +71,8 @@ class Case:
     """
 
     def __init__(self, n, f, S, count, pattern, seed, byz=None, corrupt=None, *, lens=None, too_few=None,
-                 dirty_pads=False, pos=None, honest=None):
-        assert pattern in PATTERNS + GONE_PATTERNS
+                 dirty_pads=False, pos=None, honest=None, missing=None):
+        assert pattern in PATTERNS + GONE_PATTERNS + COUNT_PATTERNS
         rng = np.random.default_rng(seed)
         k = n - 2 * f
         self.ragged = lens is not None
@@ -87,6 +93,8 @@ class Case:
         assert self.too_few <= set(range(count)) and honest <= set(range(count))
         if pattern == "kth_at":
             assert pos is not None and k - 1 <= pos < n - 1
+        if pattern == "data_missing":
+            assert len(missing) == count and all(0 <= m <= min(k, n - k) for m in missing)
         if dirty_pads:  # room for the partial dword's pad bytes and one whole lane past S_i
             assert all(self.spitch - round_up(int(s), 4) >= 4 for s in self.lens)
         d = max(self.depth, 1)
@@ -115,6 +123,8 @@ class Case:
                 absent = rng.permutation(data)[:f]
             elif pat == "parity":
                 absent = rng.permutation(par)[:f]
+            elif pat == "data_missing":
+                absent = rng.permutation(data)[:missing[i]]
             elif pat == "corrupt_data":
                 absent = rng.permutation(n)[:f]
             elif pat == "corrupt_parity":
@@ -300,12 +310,15 @@ class DevCase:
                     status=self.read_status())
 
 
-def check_against_oracle(case, got, joined=True):
+def check_against_oracle(case, got, joined=True, prefill=None):
     """Every specified row on [0, S_i), valid byte, leaf and status; the zero
     pad [S_i, spitch) of every regenerated row; for the delivered instances the
     digest, the joined value and (uniform length) its zero tail up to the pitch;
-    for a too-few instance the untouched prefill of its value and digest."""
+    for a too-few instance the untouched prefill of its value and digest
+    (DevCase's constants, or the arrays prefill["values"] / prefill["digests"])."""
     c = case
+    fill = prefill or dict(values=np.full_like(got["values"], VALUE_FILL),
+                           digests=np.full_like(got["digests"], DIGEST_FILL))
     assert np.array_equal(got["status"], c.want_status), (got["status"], c.want_status)
     assert np.array_equal(got["valid"], c.want_valid)
     want_leaves = c.want_leaves()
@@ -315,8 +328,8 @@ def check_against_oracle(case, got, joined=True):
         assert same[spec].all(), (i, np.flatnonzero(spec & ~same)[:8])
         assert np.array_equal(got["leaves"][i, spec], want_leaves[i, spec]), ("leaves", i)
         if c.want_status[i] == -3:  # skipped by every kernel after the prepare
-            assert (got["values"][i] == VALUE_FILL).all(), i
-            assert (got["digests"][i] == DIGEST_FILL).all(), i
+            assert np.array_equal(got["values"][i], fill["values"][i]), i
+            assert np.array_equal(got["digests"][i], fill["digests"][i]), i
             continue
         regen = c.want_valid[i] == 0  # absent, or the corrupted ECHO
         assert not got["pitch_rows"][i, regen, Si:].any(), ("pad of a regenerated row", i)
