@@ -174,6 +174,7 @@ constexpr int kHostSlots = RBC_HOST_SLOTS;
 struct rbc_ctx {
     int n = 0, f = 0, k = 0, p = 0, depth = 0, width = 0, device = 0;
     bool fft = false;              // additive-FFT codec active (rs_fft.hip)
+    bool fft_generic = false;      // ... in its run-time-geometry form (rs_fft_any.hip)
     // wave issue priorities (s_setprio 0..3) of the commit-side kernels
     // (encode, leaves, tree build) and the receive-side ones (verify,
     // interpolate); rbc_ctx_set_wave_priority, default 0
@@ -362,6 +363,7 @@ int stage_encode(rbc_ctx *c, hipStream_t st, int count, const uint8_t *values, u
         a.prio = c->tx_prio;
         a.parity = out.parity;
         a.parity_inst_pitch = parity_inst_pitch;
+        a.generic = c->fft_generic;
         RBC_HIP(rbc_launch_rs_fft(a, st));
         return RBC_OK;
     }
@@ -666,10 +668,11 @@ int stage_regenerate(rbc_ctx *c, Ws &w, hipStream_t st, int count, const Rows &b
             a.counter = pa.counter;
         }
         a.prio = c->reencode_prio();
+        a.generic = c->fft_generic;  // no fused join in that form: join_kernel assembles the value
         // tile 0's lanes zero the value's tail, 4 B each, and only the lanes
         // with a column inside the row pitch run (rs_fft.hip): the tail must
         // fit min(256, shard_pitch) bytes, else the separate join zero-fills it
-        if (values_out && joined && !b.lens && b.uniform_len >= kFusedJoinMinS &&
+        if (values_out && joined && !c->fft_generic && !b.lens && b.uniform_len >= kFusedJoinMinS &&
             value_pitch >= (uint64_t)c->k * b.uniform_len &&
             value_pitch - (uint64_t)c->k * b.uniform_len <= std::min<uint64_t>(256, b.pitch)) {
             a.join = values_out;
@@ -1127,12 +1130,20 @@ int rbc_ctx_set_decode_priority(rbc_ctx *c, int gemv_prio, int reencode_prio) {
 
 int rbc_ctx_set_codec(rbc_ctx *c, int codec) {
     if (!c) return RBC_ERR_INVALID_ARG;
+    const bool special = rbc_fft_supported(c->n, c->k);
+    const bool generic = rbc_fft_any_built() && rbc_fft_any_supported(c->n, c->k);
     if (codec == RBC_CODEC_MATRIX) {
-        c->fft = false;
-    } else if (codec == RBC_CODEC_AUTO || codec == RBC_CODEC_FFT) {
-        const bool ok = rbc_fft_supported(c->n, c->k);
-        if (codec == RBC_CODEC_FFT && !ok) return RBC_ERR_INVALID_ARG;
-        c->fft = ok;
+        c->fft = c->fft_generic = false;
+    } else if (codec == RBC_CODEC_AUTO) {  // never the generic form
+        c->fft = special;
+        c->fft_generic = false;
+    } else if (codec == RBC_CODEC_FFT) {
+        if (!special && !generic) return RBC_ERR_INVALID_ARG;
+        c->fft = true;
+        c->fft_generic = !special;
+    } else if (codec == RBC_CODEC_FFT_GENERIC) {
+        if (!generic) return RBC_ERR_INVALID_ARG;
+        c->fft = c->fft_generic = true;
     } else {
         return RBC_ERR_INVALID_ARG;
     }
@@ -1142,6 +1153,12 @@ int rbc_ctx_set_codec(rbc_ctx *c, int codec) {
 int rbc_ctx_codec(const rbc_ctx *c, int *codec) {
     if (!c || !codec) return RBC_ERR_INVALID_ARG;
     *codec = c->fft ? RBC_CODEC_FFT : RBC_CODEC_MATRIX;
+    return RBC_OK;
+}
+
+int rbc_ctx_fft_form(const rbc_ctx *c, int *form) {
+    if (!c || !form) return RBC_ERR_INVALID_ARG;
+    *form = !c->fft ? RBC_FFT_FORM_NONE : c->fft_generic ? RBC_FFT_FORM_GENERIC : RBC_FFT_FORM_SPECIALISED;
     return RBC_OK;
 }
 

@@ -23,6 +23,11 @@ inline bool rbc_fft_supported(int n, int k) {
     return false;
 }
 
+// The run-time-geometry transform (rs_fft_any.hip): any 1 <= k <= n with
+// 33 <= n <= 128; its width is the smallest power of two >= n.  (No W = 256
+// kernel: it does not fit the register file without scratch.)
+inline bool rbc_fft_any_supported(int n, int k) { return n >= 33 && n <= 128 && k >= 1 && k <= n; }
+
 // Trees (merkle_kernel) or instances (merkle_recheck_kernel) packed into each
 // one-wave block of `count` trees of `width` leaves: up to 512 / W (<= 64, 16 KiB
 // of node LDS), halved until the grid has >= 512 blocks so that a small batch

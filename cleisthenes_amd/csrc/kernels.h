@@ -237,6 +237,7 @@ struct FftArgs {
     // parity + inst * parity_inst_pitch + (pos - k) * row_pitch
     uint8_t *parity;           // [I][n-k][row_pitch]
     uint64_t parity_inst_pitch;
+    int generic;               // run the run-time-geometry transform (rs_fft_any.hip)
 };
 
 // VAL / ECHO marshaling (wire.hip): message (i, j) = pb.Message bytes of
@@ -365,7 +366,14 @@ struct QuorumArgs {
 enum { QUORUM_ECHO = 1, QUORUM_AMPLIFY = 2, QUORUM_SEND_READY = 4, QUORUM_DELIVER = 8 };
 hipError_t rbc_launch_quorum(const QuorumArgs &a, hipStream_t st);
 
+// a.generic == 0: rs_fft_kernel<LOGW, K, N> (rs_fft.hip, the RBC_FFT_GEOMS geometries); else it
+// hands over to rbc_launch_rs_fft_any (rs_fft_any.hip: n and k at run time, no fused join).
+// That one is a weak reference: a relink of the library from a fixed list of objects (the test
+// mutants, a host-only build) has no rs_fft_any.o; there the form counts as not built
+// (rbc_fft_any_built), and rbc_ctx_set_codec refuses it.
 hipError_t rbc_launch_rs_fft(const FftArgs &a, hipStream_t st);
+hipError_t rbc_launch_rs_fft_any(const FftArgs &a, hipStream_t st) __attribute__((weak));
+inline bool rbc_fft_any_built() { return rbc_launch_rs_fft_any != nullptr; }
 
 int rbc_gf_pick_rc(int R, int rcmax);  // GfArgs::rc; the rule is host_shared.h's rbc_gf_pick_rc_impl
 hipError_t rbc_launch_gf_rows(const GfArgs &a, hipStream_t st);

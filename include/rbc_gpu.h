@@ -86,12 +86,28 @@ int rbc_ctx_encode_matrix(const rbc_ctx *ctx, uint8_t *out);
 /* GF(2^8) codec behind encode / interpolate (same bytes either way):
  * RBC_CODEC_AUTO = additive FFT where this build has a specialised transform
  * for (n, k) (rbc_ctx_codec reports it), else the matrix kernel;
- * RBC_CODEC_MATRIX forces klauspost's encode-matrix product on the GPU. */
+ * RBC_CODEC_MATRIX forces klauspost's encode-matrix product on the GPU;
+ * RBC_CODEC_FFT = the specialised transform where there is one, else the
+ * run-time-geometry transform (any 1 <= k <= n with 33 <= n <= 128), else
+ * RBC_ERR_INVALID_ARG;
+ * RBC_CODEC_FFT_GENERIC = the run-time-geometry transform wherever it is built,
+ * at the specialised geometries too, else RBC_ERR_INVALID_ARG.
+ * AUTO never picks the run-time-geometry transform.  rbc_ctx_codec reports FFT
+ * for both transforms; rbc_ctx_fft_form tells them apart.
+ * RBC_CODEC_FFT_GENERIC and rbc_ctx_fft_form are additions within ABI 7,
+ * detected by symbol presence (RBC_HAS_FFT_ANY). */
+#define RBC_HAS_FFT_ANY 1
 #define RBC_CODEC_AUTO 0
 #define RBC_CODEC_MATRIX 1
 #define RBC_CODEC_FFT 2
+#define RBC_CODEC_FFT_GENERIC 3
 int rbc_ctx_set_codec(rbc_ctx *ctx, int codec);
 int rbc_ctx_codec(const rbc_ctx *ctx, int *codec); /* effective: MATRIX or FFT */
+/* which transform an FFT context runs */
+#define RBC_FFT_FORM_NONE 0        /* matrix codec */
+#define RBC_FFT_FORM_SPECIALISED 1 /* rs_fft_kernel<LOGW,K,N> */
+#define RBC_FFT_FORM_GENERIC 2     /* the run-time-geometry transform */
+int rbc_ctx_fft_form(const rbc_ctx *ctx, int *form);
 /* Wave issue priority (0..3, the SIMD arbiter's s_setprio level) of this
  * context's commit-side kernels (encode, leaf hashing, tree build) and
  * receive-side kernels (ECHO verify, interpolate's hashing, root recheck,
