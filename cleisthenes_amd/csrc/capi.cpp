@@ -175,6 +175,7 @@ struct rbc_ctx {
     int n = 0, f = 0, k = 0, p = 0, depth = 0, width = 0, device = 0;
     bool fft = false;              // additive-FFT codec active (rs_fft.hip)
     bool fft_generic = false;      // ... in its run-time-geometry form (rs_fft_any.hip)
+    bool fft_wide = false;         // ... that form being the wide one (rs_fft_wide.hip, n > 128); implies fft_generic
     // wave issue priorities (s_setprio 0..3) of the commit-side kernels
     // (encode, leaves, tree build) and the receive-side ones (verify,
     // interpolate); rbc_ctx_set_wave_priority, default 0
@@ -1132,18 +1133,26 @@ int rbc_ctx_set_codec(rbc_ctx *c, int codec) {
     if (!c) return RBC_ERR_INVALID_ARG;
     const bool special = rbc_fft_supported(c->n, c->k);
     const bool generic = rbc_fft_any_built() && rbc_fft_any_supported(c->n, c->k);
+    const bool wide = rbc_fft_wide_built() && rbc_fft_wide_supported(c->n, c->k);
     if (codec == RBC_CODEC_MATRIX) {
-        c->fft = c->fft_generic = false;
-    } else if (codec == RBC_CODEC_AUTO) {  // never the generic form
+        c->fft = c->fft_generic = c->fft_wide = false;
+    } else if (codec == RBC_CODEC_AUTO) {  // never a run-time-geometry form
         c->fft = special;
-        c->fft_generic = false;
+        c->fft_generic = c->fft_wide = false;
     } else if (codec == RBC_CODEC_FFT) {
         if (!special && !generic) return RBC_ERR_INVALID_ARG;
         c->fft = true;
         c->fft_generic = !special;
+        c->fft_wide = false;
     } else if (codec == RBC_CODEC_FFT_GENERIC) {
         if (!generic) return RBC_ERR_INVALID_ARG;
         c->fft = c->fft_generic = true;
+        c->fft_wide = false;
+    } else if (codec == RBC_CODEC_FFT_WIDE) {
+        // the stages see a run-time-geometry form (no fused join); rbc_launch_rs_fft picks the
+        // wide launcher by n > 128
+        if (!wide) return RBC_ERR_INVALID_ARG;
+        c->fft = c->fft_generic = c->fft_wide = true;
     } else {
         return RBC_ERR_INVALID_ARG;
     }
@@ -1158,7 +1167,10 @@ int rbc_ctx_codec(const rbc_ctx *c, int *codec) {
 
 int rbc_ctx_fft_form(const rbc_ctx *c, int *form) {
     if (!c || !form) return RBC_ERR_INVALID_ARG;
-    *form = !c->fft ? RBC_FFT_FORM_NONE : c->fft_generic ? RBC_FFT_FORM_GENERIC : RBC_FFT_FORM_SPECIALISED;
+    *form = !c->fft          ? RBC_FFT_FORM_NONE
+            : c->fft_wide    ? RBC_FFT_FORM_WIDE
+            : c->fft_generic ? RBC_FFT_FORM_GENERIC
+                             : RBC_FFT_FORM_SPECIALISED;
     return RBC_OK;
 }
 

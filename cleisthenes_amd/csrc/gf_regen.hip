@@ -215,7 +215,9 @@ __global__ __launch_bounds__(64 * NT) __attribute__((amdgpu_waves_per_eu(WPE))) 
 
 hipError_t rbc_launch_gf_regen(const GfArgs &a, hipStream_t st) {
     if (a.count <= 0 || a.R <= 0) return hipSuccess;
-    if (a.mode != GF_MODE_DECODE || !a.rcount || a.nmiss || a.copy || a.K < 1 || a.K > 248 || a.out_row_pitch % 4u)
+    // K up to 256, the largest k of n <= 256: the kernel sizes everything that depends on K from the
+    // launch (s_off holds KP + 8 row starts in the dynamic LDS below; the row indices are bytes)
+    if (a.mode != GF_MODE_DECODE || !a.rcount || a.nmiss || a.copy || a.K < 1 || a.K > 256 || a.out_row_pitch % 4u)
         return hipErrorInvalidValue;
     // one wave per column tile owns every missing row; the tile width, the rows
     // per pass and the tiles per block are host_shared.h's rbc_gf_regen_form

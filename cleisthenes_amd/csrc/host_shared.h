@@ -27,6 +27,9 @@ inline bool rbc_fft_supported(int n, int k) {
 // 33 <= n <= 128; its width is the smallest power of two >= n.  (No W = 256
 // kernel: it does not fit the register file without scratch.)
 inline bool rbc_fft_any_supported(int n, int k) { return n >= 33 && n <= 128 && k >= 1 && k <= n; }
+// The same for 129 <= n <= 256 (rs_fft_wide.hip): two 128-row halves, the idle
+// one parked in the LDS.  A form of its own, chosen only by RBC_CODEC_FFT_WIDE.
+inline bool rbc_fft_wide_supported(int n, int k) { return n >= 129 && n <= 256 && k >= 1 && k <= n; }
 
 // Trees (merkle_kernel) or instances (merkle_recheck_kernel) packed into each
 // one-wave block of `count` trees of `width` leaves: up to 512 / W (<= 64, 16 KiB

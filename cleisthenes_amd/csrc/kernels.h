@@ -237,7 +237,7 @@ struct FftArgs {
     // parity + inst * parity_inst_pitch + (pos - k) * row_pitch
     uint8_t *parity;           // [I][n-k][row_pitch]
     uint64_t parity_inst_pitch;
-    int generic;               // run the run-time-geometry transform (rs_fft_any.hip)
+    int generic;               // run the run-time-geometry transform (rs_fft_any.hip; n > 128: rs_fft_wide.hip)
 };
 
 // VAL / ECHO marshaling (wire.hip): message (i, j) = pb.Message bytes of
@@ -370,10 +370,13 @@ hipError_t rbc_launch_quorum(const QuorumArgs &a, hipStream_t st);
 // hands over to rbc_launch_rs_fft_any (rs_fft_any.hip: n and k at run time, no fused join).
 // That one is a weak reference: a relink of the library from a fixed list of objects (the test
 // mutants, a host-only build) has no rs_fft_any.o; there the form counts as not built
-// (rbc_fft_any_built), and rbc_ctx_set_codec refuses it.
+// (rbc_fft_any_built), and rbc_ctx_set_codec refuses it.  With a.generic and n > 128 it hands over
+// to rbc_launch_rs_fft_wide (rs_fft_wide.hip, 129 <= n <= 256), a weak reference in the same way.
 hipError_t rbc_launch_rs_fft(const FftArgs &a, hipStream_t st);
 hipError_t rbc_launch_rs_fft_any(const FftArgs &a, hipStream_t st) __attribute__((weak));
 inline bool rbc_fft_any_built() { return rbc_launch_rs_fft_any != nullptr; }
+hipError_t rbc_launch_rs_fft_wide(const FftArgs &a, hipStream_t st) __attribute__((weak));
+inline bool rbc_fft_wide_built() { return rbc_launch_rs_fft_wide != nullptr; }
 
 int rbc_gf_pick_rc(int R, int rcmax);  // GfArgs::rc; the rule is host_shared.h's rbc_gf_pick_rc_impl
 hipError_t rbc_launch_gf_rows(const GfArgs &a, hipStream_t st);

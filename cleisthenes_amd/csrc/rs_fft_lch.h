@@ -1,7 +1,8 @@
 // rs_fft_lch.h -- the Lin-Chung-Han additive FFT over GF(2^8)/0x11D as device
 // templates: field arithmetic and butterfly constants at compile time, the
 // constant multiply of 4 packed bytes, and the unrolled transforms.  Shared by
-// rs_fft.hip (one kernel per geometry) and rs_fft_any.hip (n and k at run time).
+// rs_fft.hip (one kernel per geometry) and, through rs_fft_rt.h, rs_fft_any.hip and
+// rs_fft_wide.hip (n and k at run time).
 #pragma once
 #include <utility>
 

@@ -301,20 +301,22 @@ class Context:
 
     def set_codec(self, codec: str) -> None:
         """"auto", "matrix", "fft" (the specialised transform where there is one,
-        else the run-time-geometry one) or "fft_generic" (the latter everywhere)."""
-        check(lib.rbc_ctx_set_codec(self._p, {"auto": 0, "matrix": 1, "fft": 2, "fft_generic": 3}[codec]),
-              "rbc_ctx_set_codec")
+        else the run-time-geometry one), "fft_generic" (the latter everywhere) or
+        "fft_wide" (the run-time-geometry transform for 129 <= N <= 256, which no
+        other name picks)."""
+        codes = {"auto": 0, "matrix": 1, "fft": 2, "fft_generic": 3, "fft_wide": 4}
+        check(lib.rbc_ctx_set_codec(self._p, codes[codec]), "rbc_ctx_set_codec")
 
     @property
     def fft_form(self) -> str:
         """Which transform the FFT codec runs: "none" (matrix codec),
-        "specialised" or "generic" (rbc_ctx_fft_form, RBC_HAS_FFT_ANY)."""
+        "specialised", "generic" or "wide" (rbc_ctx_fft_form, RBC_HAS_FFT_ANY)."""
         if not _lib.HAS_FFT_ANY:
             raise ImportError(f"{_lib.LIB_PATH} has no run-time-geometry FFT (RBC_HAS_FFT_ANY): "
                               "rbc_ctx_fft_form missing")
         f = c_int()
         check(lib.rbc_ctx_fft_form(self._p, byref(f)), "rbc_ctx_fft_form")
-        return ("none", "specialised", "generic")[f.value]
+        return ("none", "specialised", "generic", "wide")[f.value]
 
     WIRE_CODECS = ("json", "binary")
 

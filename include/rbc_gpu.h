@@ -95,18 +95,27 @@ int rbc_ctx_encode_matrix(const rbc_ctx *ctx, uint8_t *out);
  * AUTO never picks the run-time-geometry transform.  rbc_ctx_codec reports FFT
  * for both transforms; rbc_ctx_fft_form tells them apart.
  * RBC_CODEC_FFT_GENERIC and rbc_ctx_fft_form are additions within ABI 7,
- * detected by symbol presence (RBC_HAS_FFT_ANY). */
+ * detected by symbol presence (RBC_HAS_FFT_ANY).
+ * RBC_CODEC_FFT_WIDE = the run-time-geometry transform for 129 <= n <= 256
+ * (any 1 <= k <= n; two 128-row halves), at (256, 86) too; at any other n, or
+ * where it is not built, RBC_ERR_INVALID_ARG and the context stays as it was.
+ * No other codec value picks it.  rbc_ctx_codec reports FFT, rbc_ctx_fft_form
+ * RBC_FFT_FORM_WIDE.  An addition within ABI 7 (RBC_HAS_FFT_WIDE): an older
+ * library answers it with RBC_ERR_INVALID_ARG. */
 #define RBC_HAS_FFT_ANY 1
+#define RBC_HAS_FFT_WIDE 1
 #define RBC_CODEC_AUTO 0
 #define RBC_CODEC_MATRIX 1
 #define RBC_CODEC_FFT 2
 #define RBC_CODEC_FFT_GENERIC 3
+#define RBC_CODEC_FFT_WIDE 4
 int rbc_ctx_set_codec(rbc_ctx *ctx, int codec);
 int rbc_ctx_codec(const rbc_ctx *ctx, int *codec); /* effective: MATRIX or FFT */
 /* which transform an FFT context runs */
 #define RBC_FFT_FORM_NONE 0        /* matrix codec */
 #define RBC_FFT_FORM_SPECIALISED 1 /* rs_fft_kernel<LOGW,K,N> */
 #define RBC_FFT_FORM_GENERIC 2     /* the run-time-geometry transform */
+#define RBC_FFT_FORM_WIDE 3        /* the same for 129 <= n <= 256 */
 int rbc_ctx_fft_form(const rbc_ctx *ctx, int *form);
 /* Wave issue priority (0..3, the SIMD arbiter's s_setprio level) of this
  * context's commit-side kernels (encode, leaf hashing, tree build) and

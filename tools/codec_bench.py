@@ -3,7 +3,8 @@
 
 For (n, f) one context is created per codec form available there -- the matrix
 product, the specialised additive FFT (the RBC_FFT_GEOMS geometries), the
-run-time-geometry additive FFT (33 <= n <= 128) -- and three device calls are
+run-time-geometry additive FFT (33 <= n <= 128) or its wide form
+(129 <= n <= 256) -- and three device calls are
 timed with events on --instances values of --value-bytes each:
 
   encode   rbc_dev_encode alone
@@ -18,11 +19,12 @@ iteration by iteration, for --iters (>= 20) timed iterations each.  Before
 anything is reported the forms' outputs on the timed inputs are compared on the
 device: encoded shards, roots, branches, statuses, values and digests must be
 identical.  The result is one JSON line: per call and form the median, min, max
-and every iteration in ms, and per call whether the generic form's range lies
-wholly below or above the matrix codec's (and the specialised one's).
+and every iteration in ms, and per call whether the generic (or wide) form's
+range lies wholly below or above the matrix codec's (and the specialised one's).
 
   python tools/codec_bench.py --n 100 --f 33 --out profiles/fft_any/n100_f33.json
   python tools/codec_bench.py --all --out-dir profiles/fft_any
+  python tools/codec_bench.py --n 200 --f 66 --instances 256 --out profiles/fft_wide/n200_f66.json
 
 --all runs the geometries of DESIGN.md 5.1's table, each in a child process of
 its own under its own time limit, and stops at the first that fails.
@@ -135,11 +137,12 @@ def one(a):
     probe.set_codec("auto")
     if probe.fft_form == "specialised":
         codecs.append("fft")
-    try:
-        probe.set_codec("fft_generic")
-        codecs.append("fft_generic")
-    except ca.RBCError:
-        pass
+    for codec in ("fft_generic", "fft_wide"):  # the run-time-geometry form built for this n, if any
+        try:
+            probe.set_codec(codec)
+            codecs.append(codec)
+        except ca.RBCError:
+            pass
     S = (a.value_bytes + k - 1) // k
     rng = np.random.default_rng(a.seed)
     values = rng.integers(0, 256, (a.instances, rup(k * S + 32, 64)), dtype=np.uint8)
@@ -181,12 +184,14 @@ def one(a):
     for c in CALLS:
         t = res["calls"][c]
         v = {}
-        if "fft_generic" in t:
-            v["generic_vs_matrix"] = verdict(t["fft_generic"], t["matrix"])
-            v["matrix_over_generic_median"] = t["matrix"]["median_ms"] / t["fft_generic"]["median_ms"]
+        for codec, name in (("fft_generic", "generic"), ("fft_wide", "wide")):
+            if codec not in t:
+                continue
+            v[f"{name}_vs_matrix"] = verdict(t[codec], t["matrix"])
+            v[f"matrix_over_{name}_median"] = t["matrix"]["median_ms"] / t[codec]["median_ms"]
             if "fft" in t:
-                v["generic_vs_specialised"] = verdict(t["fft_generic"], t["fft"])
-                v["generic_over_specialised_median"] = t["fft_generic"]["median_ms"] / t["fft"]["median_ms"]
+                v[f"{name}_vs_specialised"] = verdict(t[codec], t["fft"])
+                v[f"{name}_over_specialised_median"] = t[codec]["median_ms"] / t["fft"]["median_ms"]
         res["verdicts"][c] = v
     line = json.dumps(res)
     print(line, flush=True)
