@@ -64,6 +64,8 @@ _SIGS = {
     "rbc_ctx_set_recheck": (c_int, [c_void_p, c_int]),
     "rbc_ctx_codec": (c_int, [c_void_p, POINTER(c_int)]),
     "rbc_ctx_fft_form": (c_int, [c_void_p, POINTER(c_int)]),  # RBC_HAS_FFT_ANY
+    "rbc_ctx_set_fft_lane": (c_int, [c_void_p, c_int]),  # RBC_HAS_FFT_SMALL
+    "rbc_ctx_fft_lane": (c_int, [c_void_p, POINTER(c_int)]),
     "rbc_dev_malloc": (c_int, [c_int, c_size_t, POINTER(c_void_p)]),
     "rbc_dev_free": (c_int, [c_void_p]),
     "rbc_dev_memset": (c_int, [c_void_p, c_int, c_size_t]),
@@ -243,7 +245,7 @@ _SIGS = {
 
 # Additions made at an unchanged ABI version are detected by symbol, as their
 # header macros say (RBC_HAS_WIRE_RX, RBC_HAS_WIRE_RECEIVE, RBC_HAS_WIRE_BINARY, RBC_HAS_WIRE_READY,
-# RBC_HAS_FFT_ANY): another build of
+# RBC_HAS_FFT_ANY, RBC_HAS_FFT_SMALL): another build of
 # ABI 7 (RBC_GPU_LIB) may lack them.  They are then left unbound, and using one
 # raises.
 _BY_SYMBOL = ("rbc_dev_unmarshal_val", "rbc_wire_rx_create", "rbc_wire_rx_destroy", "rbc_wire_validate",
@@ -260,12 +262,15 @@ HAS_WIRE_RECEIVE = all(hasattr(lib, _name) for _name in _BY_SYMBOL_RECEIVE)
 HAS_WIRE_BINARY = all(hasattr(lib, _name) for _name in _BY_SYMBOL_BINARY)
 HAS_WIRE_READY = all(hasattr(lib, _name) for _name in _BY_SYMBOL_READY)
 HAS_FFT_ANY = hasattr(lib, "rbc_ctx_fft_form")  # RBC_HAS_FFT_ANY
+_BY_SYMBOL_FFT_SMALL = ("rbc_ctx_set_fft_lane", "rbc_ctx_fft_lane")
+HAS_FFT_SMALL = all(hasattr(lib, _name) for _name in _BY_SYMBOL_FFT_SMALL)  # RBC_HAS_FFT_SMALL
 
 for _name, (_res, _args) in _SIGS.items():
     if ((_name in _BY_SYMBOL and not HAS_WIRE_RX) or (_name in _BY_SYMBOL_RECEIVE and not HAS_WIRE_RECEIVE)
             or (_name in _BY_SYMBOL_BINARY and not HAS_WIRE_BINARY)
             or (_name in _BY_SYMBOL_READY and not HAS_WIRE_READY)
-            or (_name == "rbc_ctx_fft_form" and not HAS_FFT_ANY)):
+            or (_name == "rbc_ctx_fft_form" and not HAS_FFT_ANY)
+            or (_name in _BY_SYMBOL_FFT_SMALL and not HAS_FFT_SMALL)):
         continue
     _fn = getattr(lib, _name)
     _fn.restype = _res

@@ -176,6 +176,8 @@ struct rbc_ctx {
     bool fft = false;              // additive-FFT codec active (rs_fft.hip)
     bool fft_generic = false;      // ... in its run-time-geometry form (rs_fft_any.hip)
     bool fft_wide = false;         // ... that form being the wide one (rs_fft_wide.hip, n > 128); implies fft_generic
+    bool fft_small = false;        // ... that form being the small one (rs_fft_small.hip, n <= 32); implies fft_generic
+    int fft_lane = 0;              // the small form's lane width (rbc_ctx_set_fft_lane): 0 automatic
     // wave issue priorities (s_setprio 0..3) of the commit-side kernels
     // (encode, leaves, tree build) and the receive-side ones (verify,
     // interpolate); rbc_ctx_set_wave_priority, default 0
@@ -365,6 +367,7 @@ int stage_encode(rbc_ctx *c, hipStream_t st, int count, const uint8_t *values, u
         a.parity = out.parity;
         a.parity_inst_pitch = parity_inst_pitch;
         a.generic = c->fft_generic;
+        a.lane = c->fft_lane;
         RBC_HIP(rbc_launch_rs_fft(a, st));
         return RBC_OK;
     }
@@ -670,6 +673,7 @@ int stage_regenerate(rbc_ctx *c, Ws &w, hipStream_t st, int count, const Rows &b
         }
         a.prio = c->reencode_prio();
         a.generic = c->fft_generic;  // no fused join in that form: join_kernel assembles the value
+        a.lane = c->fft_lane;
         // tile 0's lanes zero the value's tail, 4 B each, and only the lanes
         // with a column inside the row pitch run (rs_fft.hip): the tail must
         // fit min(256, shard_pitch) bytes, else the separate join zero-fills it
@@ -1134,25 +1138,33 @@ int rbc_ctx_set_codec(rbc_ctx *c, int codec) {
     const bool special = rbc_fft_supported(c->n, c->k);
     const bool generic = rbc_fft_any_built() && rbc_fft_any_supported(c->n, c->k);
     const bool wide = rbc_fft_wide_built() && rbc_fft_wide_supported(c->n, c->k);
+    const bool small = rbc_fft_small_built() && rbc_fft_small_supported(c->n, c->k);
     if (codec == RBC_CODEC_MATRIX) {
-        c->fft = c->fft_generic = c->fft_wide = false;
+        c->fft = c->fft_generic = c->fft_wide = c->fft_small = false;
     } else if (codec == RBC_CODEC_AUTO) {  // never a run-time-geometry form
         c->fft = special;
-        c->fft_generic = c->fft_wide = false;
+        c->fft_generic = c->fft_wide = c->fft_small = false;
     } else if (codec == RBC_CODEC_FFT) {
         if (!special && !generic) return RBC_ERR_INVALID_ARG;
         c->fft = true;
         c->fft_generic = !special;
-        c->fft_wide = false;
+        c->fft_wide = c->fft_small = false;
     } else if (codec == RBC_CODEC_FFT_GENERIC) {
         if (!generic) return RBC_ERR_INVALID_ARG;
         c->fft = c->fft_generic = true;
-        c->fft_wide = false;
+        c->fft_wide = c->fft_small = false;
     } else if (codec == RBC_CODEC_FFT_WIDE) {
         // the stages see a run-time-geometry form (no fused join); rbc_launch_rs_fft picks the
         // wide launcher by n > 128
         if (!wide) return RBC_ERR_INVALID_ARG;
         c->fft = c->fft_generic = c->fft_wide = true;
+        c->fft_small = false;
+    } else if (codec == RBC_CODEC_FFT_SMALL) {
+        // the same with n <= 32 and the small launcher; at (4, 1) and (16, 5) it replaces the
+        // specialised transform
+        if (!small) return RBC_ERR_INVALID_ARG;
+        c->fft = c->fft_generic = c->fft_small = true;
+        c->fft_wide = false;
     } else {
         return RBC_ERR_INVALID_ARG;
     }
@@ -1169,8 +1181,21 @@ int rbc_ctx_fft_form(const rbc_ctx *c, int *form) {
     if (!c || !form) return RBC_ERR_INVALID_ARG;
     *form = !c->fft          ? RBC_FFT_FORM_NONE
             : c->fft_wide    ? RBC_FFT_FORM_WIDE
+            : c->fft_small   ? RBC_FFT_FORM_SMALL
             : c->fft_generic ? RBC_FFT_FORM_GENERIC
                              : RBC_FFT_FORM_SPECIALISED;
+    return RBC_OK;
+}
+
+int rbc_ctx_set_fft_lane(rbc_ctx *c, int dwords) {
+    if (!c || !rbc_fft_small_built() || !rbc_fft_small_lane_valid(c->n, dwords)) return RBC_ERR_INVALID_ARG;
+    c->fft_lane = dwords;
+    return RBC_OK;
+}
+
+int rbc_ctx_fft_lane(const rbc_ctx *c, int *dwords) {
+    if (!c || !dwords) return RBC_ERR_INVALID_ARG;
+    *dwords = c->fft_lane;
     return RBC_OK;
 }
 

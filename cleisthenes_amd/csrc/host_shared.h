@@ -30,6 +30,36 @@ inline bool rbc_fft_any_supported(int n, int k) { return n >= 33 && n <= 128 && 
 // The same for 129 <= n <= 256 (rs_fft_wide.hip): two 128-row halves, the idle
 // one parked in the LDS.  A form of its own, chosen only by RBC_CODEC_FFT_WIDE.
 inline bool rbc_fft_wide_supported(int n, int k) { return n >= 129 && n <= 256 && k >= 1 && k <= n; }
+// The same for 2 <= n <= 32 (rs_fft_small.hip), at width 8, 16 or 32: the smallest
+// of them >= n.  A form of its own, chosen only by RBC_CODEC_FFT_SMALL, at (4, 1)
+// and (16, 5) too.
+inline bool rbc_fft_small_supported(int n, int k) { return n >= 2 && n <= 32 && k >= 1 && k <= n; }
+inline int rbc_fft_small_logw(int n) { return n <= 8 ? 3 : n <= 16 ? 4 : 5; }
+// Its lane width: the adjacent dword columns a lane owns, 1 (a wave covers 256 B
+// of each row) or the wider one built for the width W: 4 (1 KiB) at W = 8 and 16,
+// 2 (512 B) at W = 32, where four columns of 32 rows and of the solve's 16-row
+// copy do not fit 256 registers without scratch.  0 asks for rbc_fft_small_lane's
+// choice.
+constexpr int rbc_fft_small_wide_lane(int W) { return W <= 16 ? 4 : 2; }
+inline bool rbc_fft_small_lane_valid(int n, int lane) {
+    return lane == 0 || lane == 1 || (n <= 32 && lane == rbc_fft_small_wide_lane(1 << rbc_fft_small_logw(n)));
+}
+// The automatic choice, a function of the width W and the row pitch alone: the
+// wider lane only in the (W, row length) classes where, measured against lane 1
+// in one process, it won a call (disjoint min-max ranges) and lost none; lane 1
+// on ties, on mixed results and between the two row lengths that were measured
+// ("the small form", profiles/fft_small/):
+//   W = 8,  rows of 5.5 KB: encode and receive won, commit tied; rows of 350 KB: encode lost.
+//   W = 16: receive won at both lengths, encode or commit lost at (13, 4) and (16, 5): mixed.
+//   W = 32, rows of 95 to 150 KB: receive won at (19, 6), (25, 8), (31, 10), encode and commit
+//           tied; rows of 1.5 to 2.3 KB: receive won, encode or commit lost: mixed.
+constexpr uint32_t kFftSmallLane8MaxPitch = 8u << 10;    // W = 8: the wider lane up to here
+constexpr uint32_t kFftSmallLane32MinPitch = 64u << 10;  // W = 32: the wider lane from here
+inline int rbc_fft_small_lane(int W, uint32_t row_pitch) {
+    if (W == 8 && row_pitch <= kFftSmallLane8MaxPitch) return rbc_fft_small_wide_lane(W);
+    if (W == 32 && row_pitch >= kFftSmallLane32MinPitch) return rbc_fft_small_wide_lane(W);
+    return 1;
+}
 
 // Trees (merkle_kernel) or instances (merkle_recheck_kernel) packed into each
 // one-wave block of `count` trees of `width` leaves: up to 512 / W (<= 64, 16 KiB

@@ -237,7 +237,9 @@ struct FftArgs {
     // parity + inst * parity_inst_pitch + (pos - k) * row_pitch
     uint8_t *parity;           // [I][n-k][row_pitch]
     uint64_t parity_inst_pitch;
-    int generic;               // run the run-time-geometry transform (rs_fft_any.hip; n > 128: rs_fft_wide.hip)
+    int generic;               // run the run-time-geometry transform (rs_fft_any.hip; n > 128: rs_fft_wide.hip;
+                               // n <= 32: rs_fft_small.hip)
+    int lane;                  // rs_fft_small.hip only: dword columns per lane, 0 = rbc_fft_small_lane's choice
 };
 
 // VAL / ECHO marshaling (wire.hip): message (i, j) = pb.Message bytes of
@@ -371,12 +373,15 @@ hipError_t rbc_launch_quorum(const QuorumArgs &a, hipStream_t st);
 // That one is a weak reference: a relink of the library from a fixed list of objects (the test
 // mutants, a host-only build) has no rs_fft_any.o; there the form counts as not built
 // (rbc_fft_any_built), and rbc_ctx_set_codec refuses it.  With a.generic and n > 128 it hands over
-// to rbc_launch_rs_fft_wide (rs_fft_wide.hip, 129 <= n <= 256), a weak reference in the same way.
+// to rbc_launch_rs_fft_wide (rs_fft_wide.hip, 129 <= n <= 256), with a.generic and n <= 32 to
+// rbc_launch_rs_fft_small (rs_fft_small.hip, 2 <= n <= 32), weak references in the same way.
 hipError_t rbc_launch_rs_fft(const FftArgs &a, hipStream_t st);
 hipError_t rbc_launch_rs_fft_any(const FftArgs &a, hipStream_t st) __attribute__((weak));
 inline bool rbc_fft_any_built() { return rbc_launch_rs_fft_any != nullptr; }
 hipError_t rbc_launch_rs_fft_wide(const FftArgs &a, hipStream_t st) __attribute__((weak));
 inline bool rbc_fft_wide_built() { return rbc_launch_rs_fft_wide != nullptr; }
+hipError_t rbc_launch_rs_fft_small(const FftArgs &a, hipStream_t st) __attribute__((weak));
+inline bool rbc_fft_small_built() { return rbc_launch_rs_fft_small != nullptr; }
 
 int rbc_gf_pick_rc(int R, int rcmax);  // GfArgs::rc; the rule is host_shared.h's rbc_gf_pick_rc_impl
 hipError_t rbc_launch_gf_rows(const GfArgs &a, hipStream_t st);

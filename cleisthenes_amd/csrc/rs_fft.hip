@@ -322,6 +322,7 @@ hipError_t launch_fft(const FftArgs &a, hipStream_t st) {
 
 hipError_t rbc_launch_rs_fft(const FftArgs &a, hipStream_t st) {
     if (a.generic && a.n > 128) return rbc_fft_wide_built() ? rbc_launch_rs_fft_wide(a, st) : hipErrorInvalidValue;
+    if (a.generic && a.n <= 32) return rbc_fft_small_built() ? rbc_launch_rs_fft_small(a, st) : hipErrorInvalidValue;
     if (a.generic) return rbc_fft_any_built() ? rbc_launch_rs_fft_any(a, st) : hipErrorInvalidValue;
     if (a.count <= 0) return hipSuccess;
     if (a.row_pitch % 4) return hipErrorInvalidValue;

@@ -303,20 +303,38 @@ class Context:
         """"auto", "matrix", "fft" (the specialised transform where there is one,
         else the run-time-geometry one), "fft_generic" (the latter everywhere) or
         "fft_wide" (the run-time-geometry transform for 129 <= N <= 256, which no
-        other name picks)."""
-        codes = {"auto": 0, "matrix": 1, "fft": 2, "fft_generic": 3, "fft_wide": 4}
+        other name picks) or "fft_small" (the same for 2 <= N <= 32)."""
+        codes = {"auto": 0, "matrix": 1, "fft": 2, "fft_generic": 3, "fft_wide": 4, "fft_small": 6}
         check(lib.rbc_ctx_set_codec(self._p, codes[codec]), "rbc_ctx_set_codec")
 
     @property
     def fft_form(self) -> str:
         """Which transform the FFT codec runs: "none" (matrix codec),
-        "specialised", "generic" or "wide" (rbc_ctx_fft_form, RBC_HAS_FFT_ANY)."""
+        "specialised", "generic", "wide" or "small" (rbc_ctx_fft_form, RBC_HAS_FFT_ANY)."""
         if not _lib.HAS_FFT_ANY:
             raise ImportError(f"{_lib.LIB_PATH} has no run-time-geometry FFT (RBC_HAS_FFT_ANY): "
                               "rbc_ctx_fft_form missing")
         f = c_int()
         check(lib.rbc_ctx_fft_form(self._p, byref(f)), "rbc_ctx_fft_form")
-        return ("none", "specialised", "generic", "wide")[f.value]
+        return ("none", "specialised", "generic", "wide", "small")[f.value]
+
+    def set_fft_lane(self, dwords: int) -> None:
+        """The small form's lane width in dword columns: 0 automatic (the
+        default), 1, or the wider one built for N: 4 at N <= 16, 2 at 17 <= N <= 32
+        (rbc_ctx_set_fft_lane, RBC_HAS_FFT_SMALL)."""
+        if not _lib.HAS_FFT_SMALL:
+            raise ImportError(f"{_lib.LIB_PATH} has no small run-time-geometry FFT (RBC_HAS_FFT_SMALL): "
+                              "rbc_ctx_set_fft_lane missing")
+        check(lib.rbc_ctx_set_fft_lane(self._p, int(dwords)), "rbc_ctx_set_fft_lane")
+
+    @property
+    def fft_lane(self) -> int:
+        if not _lib.HAS_FFT_SMALL:
+            raise ImportError(f"{_lib.LIB_PATH} has no small run-time-geometry FFT (RBC_HAS_FFT_SMALL): "
+                              "rbc_ctx_fft_lane missing")
+        d = c_int()
+        check(lib.rbc_ctx_fft_lane(self._p, byref(d)), "rbc_ctx_fft_lane")
+        return d.value
 
     WIRE_CODECS = ("json", "binary")
 

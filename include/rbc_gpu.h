@@ -101,14 +101,25 @@ int rbc_ctx_encode_matrix(const rbc_ctx *ctx, uint8_t *out);
  * where it is not built, RBC_ERR_INVALID_ARG and the context stays as it was.
  * No other codec value picks it.  rbc_ctx_codec reports FFT, rbc_ctx_fft_form
  * RBC_FFT_FORM_WIDE.  An addition within ABI 7 (RBC_HAS_FFT_WIDE): an older
- * library answers it with RBC_ERR_INVALID_ARG. */
+ * library answers it with RBC_ERR_INVALID_ARG.
+ * RBC_CODEC_FFT_SMALL = the run-time-geometry transform for 2 <= n <= 32 (any
+ * 1 <= k <= n; width 8, 16 or 32), at (4, 1) and (16, 5) too, where it
+ * replaces the specialised transform; at n > 32, or where it is not built,
+ * RBC_ERR_INVALID_ARG and the context stays as it was.  No other codec value
+ * picks it: RBC_CODEC_FFT and RBC_CODEC_FFT_GENERIC keep refusing n <= 32
+ * without a specialised transform.  Its value is 6; 5 is unassigned and
+ * refused.  rbc_ctx_codec reports FFT, rbc_ctx_fft_form RBC_FFT_FORM_SMALL.
+ * An addition within ABI 7, detected by symbol (RBC_HAS_FFT_SMALL:
+ * rbc_ctx_set_fft_lane). */
 #define RBC_HAS_FFT_ANY 1
 #define RBC_HAS_FFT_WIDE 1
+#define RBC_HAS_FFT_SMALL 1
 #define RBC_CODEC_AUTO 0
 #define RBC_CODEC_MATRIX 1
 #define RBC_CODEC_FFT 2
 #define RBC_CODEC_FFT_GENERIC 3
 #define RBC_CODEC_FFT_WIDE 4
+#define RBC_CODEC_FFT_SMALL 6
 int rbc_ctx_set_codec(rbc_ctx *ctx, int codec);
 int rbc_ctx_codec(const rbc_ctx *ctx, int *codec); /* effective: MATRIX or FFT */
 /* which transform an FFT context runs */
@@ -116,7 +127,18 @@ int rbc_ctx_codec(const rbc_ctx *ctx, int *codec); /* effective: MATRIX or FFT *
 #define RBC_FFT_FORM_SPECIALISED 1 /* rs_fft_kernel<LOGW,K,N> */
 #define RBC_FFT_FORM_GENERIC 2     /* the run-time-geometry transform */
 #define RBC_FFT_FORM_WIDE 3        /* the same for 129 <= n <= 256 */
+#define RBC_FFT_FORM_SMALL 4       /* the same for 2 <= n <= 32 */
 int rbc_ctx_fft_form(const rbc_ctx *ctx, int *form);
+/* The small form's lane width: the adjacent dword columns of every row that
+ * one lane owns.  0 (the default) lets the library choose from the transform
+ * width and the row pitch; 1 and the wider width built for the context's n
+ * (4 at n <= 16, 2 at 17 <= n <= 32) force that kernel body (the wider one
+ * needs a row pitch that is a multiple of its 16 or 8 bytes, else 1 runs).
+ * Any other value, or a library without the small form: RBC_ERR_INVALID_ARG
+ * and the setting stays.  No effect on any other codec or form; a context
+ * with n > 32 accepts 0 and 1.  (RBC_HAS_FFT_SMALL) */
+int rbc_ctx_set_fft_lane(rbc_ctx *ctx, int dwords);
+int rbc_ctx_fft_lane(const rbc_ctx *ctx, int *dwords);
 /* Wave issue priority (0..3, the SIMD arbiter's s_setprio level) of this
  * context's commit-side kernels (encode, leaf hashing, tree build) and
  * receive-side kernels (ECHO verify, interpolate's hashing, root recheck,

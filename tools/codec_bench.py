@@ -3,8 +3,9 @@
 
 For (n, f) one context is created per codec form available there -- the matrix
 product, the specialised additive FFT (the RBC_FFT_GEOMS geometries), the
-run-time-geometry additive FFT (33 <= n <= 128) or its wide form
-(129 <= n <= 256) -- and three device calls are
+run-time-geometry additive FFT (33 <= n <= 128), its wide form
+(129 <= n <= 256) or its small form (2 <= n <= 32), the last once per lane
+width of --lane as "fft_small@<lane>" -- and three device calls are
 timed with events on --instances values of --value-bytes each:
 
   encode   rbc_dev_encode alone
@@ -19,12 +20,15 @@ iteration by iteration, for --iters (>= 20) timed iterations each.  Before
 anything is reported the forms' outputs on the timed inputs are compared on the
 device: encoded shards, roots, branches, statuses, values and digests must be
 identical.  The result is one JSON line: per call and form the median, min, max
-and every iteration in ms, and per call whether the generic (or wide) form's
-range lies wholly below or above the matrix codec's (and the specialised one's).
+and every iteration in ms, and per call whether the generic (or wide, or small)
+form's range lies wholly below or above the matrix codec's (and the specialised
+one's), and the small form's wider lane against its lane 1.
 
   python tools/codec_bench.py --n 100 --f 33 --out profiles/fft_any/n100_f33.json
   python tools/codec_bench.py --all --out-dir profiles/fft_any
   python tools/codec_bench.py --n 200 --f 66 --instances 256 --out profiles/fft_wide/n200_f66.json
+  python tools/codec_bench.py --n 19 --f 6 --out profiles/fft_small/n19_f6_1m.json
+  python tools/codec_bench.py --n 19 --f 6 --value-bytes 16384 --lane 1 --out profiles/fft_small/n19_f6_16k.json
 
 --all runs the geometries of DESIGN.md 5.1's table, each in a child process of
 its own under its own time limit, and stops at the first that fails.
@@ -51,9 +55,12 @@ class Form:
     """One codec form's context and its own device buffers."""
 
     def __init__(self, ca, np, a, codec, values, present, corrupt):
-        self.ca, self.np, self.codec = ca, np, codec
+        self.ca, self.np, self.codec = ca, np, codec  # codec: a set_codec name, or "fft_small@<lane>"
         self.ctx = ctx = ca.Context(a.n, a.f)
-        ctx.set_codec(codec)
+        name, _, lane = codec.partition("@")
+        ctx.set_codec(name)
+        if lane:
+            ctx.set_fft_lane(int(lane))
         self.form = ctx.fft_form
         n, k, I = a.n, ctx.k, a.instances
         self.n, self.k, self.I, self.B = n, k, I, a.value_bytes
@@ -143,6 +150,19 @@ def one(a):
             codecs.append(codec)
         except ca.RBCError:
             pass
+    small = []
+    try:
+        probe.set_codec("fft_small")
+        for lane in a.lane if a.lane else (1, 2, 4):  # default: every lane width built for this n
+            try:
+                probe.set_fft_lane(lane)
+                small.append(f"fft_small@{lane}")
+            except ca.RBCError:
+                if a.lane:
+                    raise SystemExit(f"codec_bench: lane {lane} is not built for n = {a.n}")
+    except ca.RBCError:
+        pass
+    codecs += small
     S = (a.value_bytes + k - 1) // k
     rng = np.random.default_rng(a.seed)
     values = rng.integers(0, 256, (a.instances, rup(k * S + 32, 64)), dtype=np.uint8)
@@ -192,6 +212,15 @@ def one(a):
             if "fft" in t:
                 v[f"{name}_vs_specialised"] = verdict(t[codec], t["fft"])
                 v[f"{name}_over_specialised_median"] = t[codec]["median_ms"] / t["fft"]["median_ms"]
+        for codec in small:
+            v[f"{codec}_vs_matrix"] = verdict(t[codec], t["matrix"])
+            v[f"matrix_over_{codec}_median"] = t["matrix"]["median_ms"] / t[codec]["median_ms"]
+            if "fft" in t:
+                v[f"{codec}_vs_specialised"] = verdict(t[codec], t["fft"])
+                v[f"{codec}_over_specialised_median"] = t[codec]["median_ms"] / t["fft"]["median_ms"]
+            if codec != "fft_small@1" and "fft_small@1" in t:
+                v[f"{codec}_vs_fft_small@1"] = verdict(t[codec], t["fft_small@1"])
+                v[f"fft_small@1_over_{codec}_median"] = t["fft_small@1"]["median_ms"] / t[codec]["median_ms"]
         res["verdicts"][c] = v
     line = json.dumps(res)
     print(line, flush=True)
@@ -210,6 +239,8 @@ def main():
     p.add_argument("--warmup", type=int, default=2)
     p.add_argument("--iters", type=int, default=20)
     p.add_argument("--seed", type=int, default=20261020)
+    p.add_argument("--lane", type=int, nargs="*", default=None,
+                   help="the small form's lane widths to run (default: 1 and the wider one built for n)")
     p.add_argument("--out", default=None)
     p.add_argument("--all", action="store_true", help="every geometry of DESIGN.md 5.1's table, one child each")
     p.add_argument("--out-dir", default=os.path.join(ROOT, "profiles", "fft_any"))
